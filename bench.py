@@ -23,9 +23,14 @@ max of the step time and the sum of the bytes.
 
 Prints ONE JSON line on rank 0 (contract in the task description), including
 `roofline` (algorithmic HBM bytes per launch / HIP-event kernel time vs the
-8 TB/s HBM peak) and `cpu_baseline` (the reference library's CPU path,
-oracle/_ref/ref_tool bench1 = bench/aead.cc's BM_SpeedAEAD, one pinned
-process per physical host core, rank 0 at N=1 only).
+8 TB/s HBM peak).  A plain run sets up, warms up, times the steps and prints
+the line.  `--full` adds what the headline figure does not need: `parity`
+(the digest of the timed output against the reference library's digest of the
+same records, on every rank) and `cpu_baseline` (the reference library's CPU
+path, oracle/_ref/ref_tool bench1 = bench/aead.cc's BM_SpeedAEAD, one pinned
+process per physical host core, rank 0 at N=1 only).  `--dump-outputs DIR`
+writes what the last timed step computed (output bytes, tags, per-record
+status) as DIR/<name>.npy, a fixed seeded sample where the output is large.
 """
 import argparse
 import json
@@ -611,6 +616,39 @@ def reduce_parity(code, text, world, rank):
     return worst, summary, texts
 
 
+# --dump-outputs: most elements written per array (float32 on disk, so at most
+# 32 + 16 + 4 MiB in all) and the seed of the sample positions.
+DUMP_MAX_ELEMS = {"out": 1 << 23, "tags": 1 << 22, "status": 1 << 20}
+DUMP_SEED = 0x5EA1
+
+
+def dump_outputs(w, out_dir, rank=0):
+    """Write what a caller of the timed op receives after the last timed step
+    as <out_dir>/<name>.npy (float32): `out` = the bytes of the output buffer
+    (ciphertext for seal, recovered plaintext for open; records at their batch
+    offsets, the zero padding between them included), `tags` = the 16-byte
+    tags in record order (seal only; open reads them) and `status` = the
+    per-record status bytes.  An array longer than its DUMP_MAX_ELEMS entry is
+    sampled at sorted positions drawn once from a generator seeded with
+    DUMP_SEED, so two runs with the same arguments write the same positions.
+    Ranks other than 0 of a multi-GPU run write <name>.rank<r>.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = w.nrec
+    d_back = getattr(w, "d_back", None)
+    arrays = {"out": w.d_ct if d_back is None else d_back, "status": w.d_status[:n]}
+    if d_back is None:
+        arrays["tags"] = w.d_tags[:16 * n]
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+    suffix = f".rank{rank}" if rank else ""
+    for name in sorted(arrays):
+        t, cap = arrays[name], DUMP_MAX_ELEMS[name]
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=gen).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.cpu().numpy().astype(np.float32))
+
+
 def plan_only(args, world, rank):
     """The launcher/plan/reduction path without a GPU (gloo)."""
     dist = _dist()
@@ -644,9 +682,16 @@ def main():
                          "config4/config5)")
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
                     help="seconds per CPU-baseline measurement (seal, then open)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the sealed output against the "
+                         "reference digest (parity) and measure the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of large outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the digest check of the sealed output after the timed steps")
+                    help="with --full: skip the digest check of the sealed output")
     ap.add_argument("--plan-only", action="store_true",
                     help="launcher + shard plan + reductions on CPU (gloo), no GPU")
     ap.add_argument("--op", default="seal", choices=["seal", "open"],
@@ -716,11 +761,13 @@ def main():
         raise SystemExit(f"{args.op} reported failed records")
     if args.op == "open" and not torch.equal(wl.d_back, wl.d_pt):
         raise SystemExit("open did not return the plaintext")
-    # Bit-exact check of the timed output (seal), on every rank: the digest of
-    # the rank's sealed records and tags against the reference library's
-    # digest of the same records (tests/golden/ref_shard_digests.json,
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank)
+    # Bit-exact check of the timed output (seal, --full), on every rank: the
+    # digest of the rank's sealed records and tags against the reference
+    # library's digest of the same records (tests/golden/ref_shard_digests.json,
     # ref_digests.json); reduced over ranks below.
-    if args.op == "seal" and not args.no_parity:
+    if args.full and args.op == "seal" and not args.no_parity:
         p_code, p_text = verify_workload(wl)
     else:
         p_code, p_text = PARITY_UNCHECKED, "not_checked"
@@ -766,7 +813,7 @@ def main():
                      "avg_kernel_ms": round(avg_kernel_ms, 4),
                      "compute_bound": compute_bound},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(aead, length, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)

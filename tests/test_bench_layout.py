@@ -91,6 +91,32 @@ def test_bench_shard_of_multi_gpu_run(config, world, rank):
     torch.cuda.empty_cache()
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: the arrays written are the sealed batch's
+    output buffer, tags and status as float32; an array above its element cap
+    is sampled at the same seeded positions on every call."""
+    dev = torch.device(DEV)
+    w = bench.build_workload("config3", 0, 1, 100, dev)
+    w.op(w.batch, torch.cuda.current_stream())
+    torch.cuda.synchronize()
+    assert bool(w.d_status[:w.nrec].all())
+    ct, tags = w.d_ct.cpu().numpy(), w.d_tags.cpu().numpy()
+    assert ct.size == 100 * 1408 and ct.any()
+    bench.dump_outputs(w, str(tmp_path / "whole"))
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in ("out", "tags", "status")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["out"], ct) and np.array_equal(got["tags"], tags)
+    assert np.array_equal(got["status"], np.ones(100))
+    monkeypatch.setitem(bench.DUMP_MAX_ELEMS, "out", 1000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(w, str(tmp_path / d))
+    s1, s2 = (np.load(tmp_path / d / "out.npy") for d in ("s1", "s2"))
+    idx = torch.randint(0, ct.size, (1000,),
+                        generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values
+    assert np.array_equal(s1, s2) and np.array_equal(s1, ct[idx.numpy()])
+    assert np.array_equal(np.load(tmp_path / "s1" / "tags.npy"), tags)
+
+
 def _uniform_case(aead, n, rlen, stride, ad_len, seed):
     rng = np.random.default_rng(seed)
     key = rng.integers(0, 256, size=AEAD_KEYLEN[aead], dtype=np.uint8).tobytes()

@@ -22,7 +22,7 @@ for s in $STEPS; do
     micro) run micro 300 tools/micro/${MICRO:-bs16_rate} ;;
     smoke) run smoke 400 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) run pytest 1500 python -u -m pytest tests/ -v -m gpu -rf --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} ;;
-    bench) run bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) run bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} ;;
     pmc)
       PB="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --records ${PMC_RECORDS:-262144} ${BENCH_ARGS:-}"

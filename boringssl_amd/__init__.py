@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "EVP_aead_aes_128_gcm", "EVP_aead_aes_192_gcm", "EVP_aead_aes_256_gcm",
     "EVP_aead_chacha20_poly1305", "EVP_aead_xchacha20_poly1305",
     "EVP_aead_aes_128_gcm_siv", "EVP_aead_aes_256_gcm_siv", "EVP_aead_aes_128_gcm_tls12", "EVP_aead_aes_256_gcm_tls12",
+    "EVP_aead_aes_128_ccm_bluetooth", "EVP_aead_aes_128_ccm_bluetooth_8",
+    "EVP_aead_aes_128_ccm_matter", "EVP_aead_aes_128_eax", "EVP_aead_aes_256_eax",
     "EVP_aead_aes_128_gcm_tls13", "EVP_aead_aes_256_gcm_tls13",
     "EVP_AEAD_key_length", "EVP_AEAD_nonce_length", "EVP_AEAD_max_overhead",
     "EVP_AEAD_max_tag_len", "EVP_AEAD_CTX_zero", "EVP_AEAD_CTX_new", "EVP_AEAD_CTX_free",
@@ -195,6 +197,11 @@ AEADS = {
     "xchacha20-poly1305": _lib.EVP_aead_xchacha20_poly1305,
     "aes-128-gcm-siv": _lib.EVP_aead_aes_128_gcm_siv,
     "aes-256-gcm-siv": _lib.EVP_aead_aes_256_gcm_siv,
+    "aes-128-ccm-bluetooth": _lib.EVP_aead_aes_128_ccm_bluetooth,
+    "aes-128-ccm-bluetooth-8": _lib.EVP_aead_aes_128_ccm_bluetooth_8,
+    "aes-128-ccm-matter": _lib.EVP_aead_aes_128_ccm_matter,
+    "aes-128-eax": _lib.EVP_aead_aes_128_eax,
+    "aes-256-eax": _lib.EVP_aead_aes_256_eax,
     "aes-128-gcm-tls12": _lib.EVP_aead_aes_128_gcm_tls12,
     "aes-256-gcm-tls12": _lib.EVP_aead_aes_256_gcm_tls12,
     "aes-128-gcm-tls13": _lib.EVP_aead_aes_128_gcm_tls13,

@@ -82,6 +82,12 @@ const evp_aead_st kChaChaPoly = {32, 12, 16, 16, kAeadChaChaPoly, 0};
 const evp_aead_st kXChaChaPoly = {32, 24, 16, 16, kAeadXChaChaPoly, 0};  // e_chacha20poly1305.cc:385-399
 const evp_aead_st kAes128GcmSiv = {16, 12, 16, 16, kAeadAesGcmSiv, 0};  // e_aesgcmsiv.cc:869-899
 const evp_aead_st kAes256GcmSiv = {32, 12, 16, 16, kAeadAesGcmSiv, 0};
+// e_aesccm.cc.inc:390-452 (L = 2; M = 4, 8, 16) and e_aeseax.cc:317-347.
+const evp_aead_st kAes128CcmBluetooth = {16, 13, 4, 4, kAeadAesCcm, 0};
+const evp_aead_st kAes128CcmBluetooth8 = {16, 13, 8, 8, kAeadAesCcm, 0};
+const evp_aead_st kAes128CcmMatter = {16, 13, 16, 16, kAeadAesCcm, 0};
+const evp_aead_st kAes128Eax = {16, 16, 16, 16, kAeadAesEax, 0};
+const evp_aead_st kAes256Eax = {32, 16, 16, 16, kAeadAesEax, 0};
 const evp_aead_st kAes128GcmTls12 = {16, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes256GcmTls12 = {32, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes128GcmTls13 = {16, 12, 16, 16, kAeadAesGcm, 13};
@@ -93,7 +99,7 @@ struct KeyMaterial {
   int device;  // the HIP device the key material lives on
   size_t num_keys;
   int nr;
-  void *dev;  // GcmKeyDev[num_keys] or ChaChaKeyDev[num_keys]
+  void *dev;  // GcmKeyDev[num_keys], CbcKeyDev[num_keys] or ChaChaKeyDev[num_keys]
   size_t bytes;
 };
 
@@ -133,6 +139,10 @@ static_assert(sizeof(CtxState) <= sizeof(((EVP_AEAD_CTX *)nullptr)->state), "sta
 
 CtxState *state_of(const EVP_AEAD_CTX *ctx) {
   return reinterpret_cast<CtxState *>(const_cast<uint8_t *>(ctx->state.opaque));
+}
+
+bool is_cbcmac(const EVP_AEAD *aead) {
+  return aead->kind == kAeadAesCcm || aead->kind == kAeadAesEax;
 }
 
 // Key material of num_keys keys on the current device.  AES-GCM(-SIV) key
@@ -180,6 +190,17 @@ KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_key
     GcmKeyDev *h = reinterpret_cast<GcmKeyDev *>(host.data());
     for (size_t i = 0; i < num_keys; i++) {
       if (!gcm_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
+        delete km;
+        return nullptr;
+      }
+    }
+    km->nr = (int)h[0].nr;
+  } else if (is_cbcmac(aead)) {  // host key setup only, 336 B per key
+    bytes = num_keys * sizeof(CbcKeyDev);
+    host.resize(bytes);
+    CbcKeyDev *h = reinterpret_cast<CbcKeyDev *>(host.data());
+    for (size_t i = 0; i < num_keys; i++) {
+      if (!cbc_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
         delete km;
         return nullptr;
       }
@@ -278,6 +299,10 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
   } else if (km->aead->kind == kAeadAesGcmSiv) {
     rc = launch_gcm_siv(static_cast<const GcmKeyDev *>(km->dev), d, open, km->nr, stream, ev);
     t_timing.last_name = "gcm_siv_kernel";
+  } else if (is_cbcmac(km->aead)) {
+    rc = launch_cbcmac(static_cast<const CbcKeyDev *>(km->dev), d, km->aead->kind == kAeadAesEax,
+                       open, km->nr, stream, ev);
+    t_timing.last_name = "cbcmac_kernel";
   } else {
     rc = launch_chacha(static_cast<const ChaChaKeyDev *>(km->dev), d, open,
                        km->aead->kind == kAeadXChaChaPoly, stream, ev);
@@ -326,7 +351,7 @@ int run_batch(const KeyMaterial *km, size_t tag_len, const BSSL_AMD_BATCH *batch
     // (*done_armed tells one_record whether to spin on it).
     const AeadKind k = km->aead->kind;
     const bool writes = k == kAeadAesGcm ? gcm_takes_one_record_kernel(d, gcm_eng)
-                        : k == kAeadAesGcmSiv ? false
+                        : k == kAeadAesGcmSiv || is_cbcmac(km->aead) ? false
                                               : chacha_takes_one_record_kernel(d);
     d.done = writes ? one->done : nullptr;
     if (done_armed) *done_armed = d.done != nullptr;
@@ -355,6 +380,16 @@ bool check_batch(const EVP_AEAD *aead, const BSSL_AMD_BATCH *b) {
   if (aead->kind == kAeadAesGcm) {
     if (b->nonce_len == 0) {  // e_aes.cc.inc:790-793
       PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
+      return false;
+    }
+  } else if (aead->kind == kAeadAesCcm) {
+    if (b->nonce_len != 13) {  // e_aesccm.cc.inc:331-334, 360-363
+      PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
+      return false;
+    }
+  } else if (aead->kind == kAeadAesEax) {
+    if (b->nonce_len != 12 && b->nonce_len != 16) {  // e_aeseax.cc:234-237, 281-284
+      PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
       return false;
     }
   } else if (b->nonce_len != aead->nonce_len) {  // e_chacha20poly1305.cc:127-130, 241-244
@@ -691,6 +726,20 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
       PUT_ERROR(CIPHER_R_TOO_LARGE);
       return false;
     }
+  } else if (aead->kind == kAeadAesCcm) {
+    if ((uint64_t)in_len > kCcmMaxInput) {  // e_aesccm.cc.inc:320-324, 354-358
+      PUT_ERROR(CIPHER_R_TOO_LARGE);
+      return false;
+    }
+    if (nonce_len != 13) {  // :331-334, 360-363
+      PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
+      return false;
+    }
+  } else if (aead->kind == kAeadAesEax) {
+    if (nonce_len != 12 && nonce_len != 16) {  // e_aeseax.cc:234-237, 281-284
+      PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
+      return false;
+    }
   } else {
     if (nonce_len != aead->nonce_len) {  // 12, or 24 for XChaCha (e_chacha20poly1305.cc:241)
       PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
@@ -706,8 +755,15 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
 
 // The per-AEAD tag-length rule of init (e_aes.cc.inc:742-749,
 // e_chacha20poly1305.cc:51-57, e_aesgcmsiv.cc:542-548): 0 means the maximum.
+// CCM takes its M only (e_aesccm.cc.inc:287-294), EAX 16 only
+// (e_aeseax.cc:72-79).
 bool resolve_tag_len(const EVP_AEAD *aead, size_t *tag_len) {
   if (*tag_len == EVP_AEAD_DEFAULT_TAG_LENGTH) *tag_len = aead->max_tag_len;
+  if (is_cbcmac(aead)) {
+    if (*tag_len == aead->max_tag_len) return true;
+    PUT_ERROR(aead->kind == kAeadAesCcm ? CIPHER_R_TAG_TOO_LARGE : CIPHER_R_UNSUPPORTED_TAG_SIZE);
+    return false;
+  }
   if (*tag_len > aead->max_tag_len || (aead->kind == kAeadAesGcmSiv && *tag_len != 16)) {
     PUT_ERROR(aead->kind == kAeadAesGcm || aead->kind == kAeadAesGcmSiv ? CIPHER_R_TAG_TOO_LARGE
                                                                        : CIPHER_R_TOO_LARGE);
@@ -729,6 +785,11 @@ const EVP_AEAD *EVP_aead_chacha20_poly1305(void) { return &kChaChaPoly; }
 const EVP_AEAD *EVP_aead_xchacha20_poly1305(void) { return &kXChaChaPoly; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_siv(void) { return &kAes128GcmSiv; }
 const EVP_AEAD *EVP_aead_aes_256_gcm_siv(void) { return &kAes256GcmSiv; }
+const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth(void) { return &kAes128CcmBluetooth; }
+const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth_8(void) { return &kAes128CcmBluetooth8; }
+const EVP_AEAD *EVP_aead_aes_128_ccm_matter(void) { return &kAes128CcmMatter; }
+const EVP_AEAD *EVP_aead_aes_128_eax(void) { return &kAes128Eax; }
+const EVP_AEAD *EVP_aead_aes_256_eax(void) { return &kAes256Eax; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void) { return &kAes128GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void) { return &kAes256GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void) { return &kAes128GcmTls13; }
@@ -895,6 +956,9 @@ int EVP_AEAD_CTX_openv_detached(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iov
       // The tls variants share aead_aes_gcm_openv_detached, which accepts any
       // non-empty nonce (e_aes.cc.inc:869-882).
     }
+  } else if (ctx->aead->kind == kAeadAesEax && in_tag_len != ctx->tag_len) {
+    PUT_ERROR(CIPHER_R_BAD_DECRYPT);  // before the nonce check, e_aeseax.cc:276-284
+    return 0;
   } else if (!aead_record_checks(ctx, nonce_len, total)) {
     return 0;
   }
@@ -1224,7 +1288,12 @@ IovBatchDesc iov_desc(const BSSL_AMD_IOV_BATCH *b) {
 // aead.cc.inc:316-361 (sealv) for a batch of device records.
 int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_BATCH *batch,
                                     void *hip_stream) {
-  if (!ctx || !ctx->aead || !check_iov_batch(ctx->aead, batch)) return 0;
+  if (!ctx || !ctx->aead) return 0;
+  if (is_cbcmac(ctx->aead)) {  // no iovec walk in cbcmac.hip: nothing is launched
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
+    return 0;
+  }
+  if (!check_iov_batch(ctx->aead, batch)) return 0;
   if (batch->num_records == 0) return 1;
   CtxState *st = state_of(ctx);
   if (!on_key_device(st->km)) return 0;
@@ -1261,7 +1330,12 @@ int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_
 // tags (tag_len bytes each) are read at tags + i*tag_len.
 int EVP_AEAD_CTX_openv_detached_batch_device(const EVP_AEAD_CTX *ctx,
                                              const BSSL_AMD_IOV_BATCH *batch, void *hip_stream) {
-  if (!ctx || !ctx->aead || !check_iov_batch(ctx->aead, batch)) return 0;
+  if (!ctx || !ctx->aead) return 0;
+  if (is_cbcmac(ctx->aead)) {
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
+    return 0;
+  }
+  if (!check_iov_batch(ctx->aead, batch)) return 0;
   if (batch->num_records == 0) return 1;
   if (!on_key_device(state_of(ctx)->km)) return 0;
   const int rc = iov_batch_run(

@@ -11,6 +11,8 @@
 //               (crypto/fipsmodule/aes/internal.h:325-334), re-laid-out for the
 //               LDS-table GHASH of gcm.hip.
 //   ChaChaKeyDev one per ChaCha20-Poly1305 key (32 bytes).
+//   CbcKeyDev   one per AES-CCM / AES-EAX key (336 bytes): the plain round
+//               keys and EAX's per-key constants (cbcmac.hip).
 //   BatchDesc   the record-batch descriptor passed by value to the kernels.
 #ifndef BSSL_AMD_INTERNAL_H
 #define BSSL_AMD_INTERNAL_H
@@ -58,11 +60,29 @@ struct alignas(16) ChaChaKeyDev {
   uint32_t k[8];
 };
 
+// One per AES-CCM / AES-EAX key (336 bytes; cbcmac.hip): the FIPS-197 schedule
+// as little-endian words, unrotated, and for EAX the per-key constants of
+// aead_aes_eax_init (crypto/cipher/e_aeseax.cc:87-93) B = 2L, P = 4L
+// (L = E_K(0^128)) and the OMAC chain values after the tag block,
+// E_K(0^15 || t) for t = 0, 1, 2 -- all as little-endian words of their bytes.
+// (Not GcmKeyDev: these AEADs read none of its 12.5 KB of GHASH tables.)
+struct alignas(16) CbcKeyDev {
+  uint32_t rk[15][4];
+  uint32_t nr;
+  uint32_t pad[3];
+  uint32_t eax_b[4];
+  uint32_t eax_p[4];
+  uint32_t eax_e[3][4];
+};
+static_assert(sizeof(CbcKeyDev) == 240 + 16 + 32 + 48, "layout");
+
 enum AeadKind : int {
   kAeadAesGcm = 0,
   kAeadChaChaPoly = 1,
   kAeadXChaChaPoly = 2,
-  kAeadAesGcmSiv = 3
+  kAeadAesGcmSiv = 3,
+  kAeadAesCcm = 4,
+  kAeadAesEax = 5
 };
 
 // Device chunk descriptors of iovec records: CRYPTO_IOVEC / CRYPTO_IVEC
@@ -221,6 +241,13 @@ inline bool wants_length_order(const BatchDesc &b) {
 // AES-GCM-SIV (gcm_siv.hip); uses GcmKeyDev::rk_plain of the master key.
 int launch_gcm_siv(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr, void *stream,
                    const KernelEvents *ev);
+// AES-CCM (L = 2; tag_len = M) and AES-EAX (cbcmac.hip), one lane per record.
+// BatchDesc::extra and ::iovecs are not supported (error 1); ::done is never
+// written.
+int launch_cbcmac(const CbcKeyDev *keys, const BatchDesc &b, bool eax, bool open, int nr,
+                  void *stream, const KernelEvents *ev);
+// CCM's message limit with L = 2 (CRYPTO_ccm128_max_input).
+constexpr uint64_t kCcmMaxInput = 65535;
 // xchacha: XChaCha20-Poly1305 (24-byte nonces, per-record HChaCha20 subkey).
 int launch_chacha(const ChaChaKeyDev *keys, const BatchDesc &b, bool open, bool xchacha,
                   void *stream, const KernelEvents *ev);
@@ -304,6 +331,8 @@ bool gcm_key_setup(const uint8_t *key, size_t key_len, GcmKeyDev *out);
 int gcm_key_setup_device(const uint8_t *keys, size_t key_len, size_t n, GcmKeyDev *out,
                          hipStream_t s);
 void chacha_key_setup(const uint8_t *key, ChaChaKeyDev *out);
+// AES-CCM / AES-EAX key (host only); false for a bad key length.
+bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out);
 // Key counts from which make_keys builds AES-GCM tables on the device.
 constexpr size_t kDeviceKeySetupMin = 64;
 

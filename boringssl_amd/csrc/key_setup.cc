@@ -22,6 +22,49 @@ bool gcm_key_setup(const uint8_t *key, size_t key_len, GcmKeyDev *out) {
 
 namespace {
 
+// The block times x in GF(2^128) as EAX / OMAC order it (the 16 bytes as one
+// big-endian integer, reduced by 0x87; mult_by_X, e_aeseax.cc:50-61), on
+// little-endian words of the bytes.  No branch on the (secret) top bit.
+void eax_dbl(const uint32_t in[4], uint32_t out[4]) {
+  uint32_t be[4];
+  for (int i = 0; i < 4; i++) be[i] = ks_bswap(in[i]);
+  const uint32_t carry = 0u - (be[0] >> 31);
+  for (int i = 0; i < 3; i++) be[i] = (be[i] << 1) | (be[i + 1] >> 31);
+  be[3] = (be[3] << 1) ^ (carry & 0x87u);
+  for (int i = 0; i < 4; i++) out[i] = ks_bswap(be[i]);
+  secure_zero(be, sizeof(be));
+}
+
+}  // namespace
+
+// aead_aes_ccm_init / aead_aes_eax_init (e_aesccm.cc.inc:275-308,
+// e_aeseax.cc:63-95): the key schedule, and EAX's B, P and first-block values
+// (computed for CCM keys too; nothing reads them there).
+bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out) {
+  uint32_t rk[60];
+  const int nr = ks_expand(key, (int)key_len, rk);
+  if (!nr) return false;
+  memset(out, 0, sizeof(*out));
+  for (int r = 0; r <= nr; r++)
+    for (int c = 0; c < 4; c++) out->rk[r][c] = rk[4 * r + c];
+  out->nr = (uint32_t)nr;
+  uint32_t l[4] = {0, 0, 0, 0};
+  ks_encrypt(rk, nr, l);
+  eax_dbl(l, out->eax_b);
+  eax_dbl(out->eax_b, out->eax_p);
+  for (uint32_t t = 0; t < 3; t++) {
+    uint32_t s[4] = {0, 0, 0, t << 24};  // byte 15 = t
+    ks_encrypt(rk, nr, s);
+    for (int c = 0; c < 4; c++) out->eax_e[t][c] = s[c];
+    secure_zero(s, sizeof(s));
+  }
+  secure_zero(rk, sizeof(rk));
+  secure_zero(l, sizeof(l));
+  return true;
+}
+
+namespace {
+
 // Key i's tables from raw key bytes keys[i * key_len ...].  The tables are
 // written by their own lane (12,816 B each, scattered 16-byte stores that
 // L2 merges into full lines).

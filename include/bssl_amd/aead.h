@@ -77,6 +77,21 @@ BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_chacha20_poly1305(void);  /* aead.h:126
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_xchacha20_poly1305(void); /* aead.h:130 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_siv(void);    /* aead.h:142 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_gcm_siv(void);    /* aead.h:145 */
+/* AES-CCM (RFC 3610, L = 2: 13-byte nonces, messages up to 65535 bytes; tags
+ * of 4, 8 and 16 bytes) and AES-EAX (16-byte tags; 16-byte nonces, 12-byte
+ * ones also accepted; no message limit).  Per-call rules as in the reference
+ * (e_aesccm.cc.inc:275-383, e_aeseax.cc:63-95, 221-315): a tag_len other than
+ * 0 or the AEAD's own fails init with CIPHER_R_TAG_TOO_LARGE (CCM) /
+ * CIPHER_R_UNSUPPORTED_TAG_SIZE (EAX); CCM: a longer message is
+ * CIPHER_R_TOO_LARGE, another nonce length CIPHER_R_INVALID_NONCE_SIZE; EAX:
+ * another nonce length is CIPHER_R_UNSUPPORTED_NONCE_SIZE.  They work with
+ * every host call, the contiguous device batches and keysets below; the iovec
+ * device batches and the TLS record layer (tls.h) reject them. */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth(void);   /* aead.h:174 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth_8(void); /* aead.h:179 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ccm_matter(void);      /* aead.h:183 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_eax(void);             /* aead.h:192 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_eax(void);             /* aead.h:197 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void);  /* aead.h:583 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void);  /* aead.h:584 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void);  /* aead.h:585 */
@@ -190,7 +205,8 @@ BSSL_AMD_EXPORT void ERR_clear_error(void);
  * tag at tags + i*tag_len (tag_len = the context's tag length).  status[i]
  * (optional) receives 1 on success, 0 on failure (authentication failure on
  * open, or a per-record limit exceeded: GCM 2^36-32 bytes gcm.cc.inc:409,
- * ChaCha20-Poly1305 2^38-64 bytes e_chacha20poly1305.cc:138); a failed
+ * ChaCha20-Poly1305 2^38-64 bytes e_chacha20poly1305.cc:138, AES-CCM 65535
+ * bytes e_aesccm.cc.inc:320); a failed
  * record's output (and, for seal, tag) is zero-filled, as the reference does
  * for a failed single call (aead.cc.inc:132-139, 539-547). */
 typedef struct bssl_amd_batch_st {
@@ -249,7 +265,10 @@ BSSL_AMD_EXPORT int EVP_AEAD_CTX_open_batch_device(const EVP_AEAD_CTX *ctx,
  * (no staging copy, no gather/scatter pass); the call only enqueues work on
  * `hip_stream` (one small kernel for the per-record totals, then the bulk
  * kernels) and never synchronises it.  Chunks of one batch must not partially
- * overlap (aead.cc.inc:281-308; not checked on the device). */
+ * overlap (aead.cc.inc:281-308; not checked on the device).
+ * Not implemented for the AES-CCM and AES-EAX contexts: both calls return 0
+ * with CIPHER_R_CTRL_NOT_IMPLEMENTED and launch nothing (their host sealv /
+ * openv calls gather the chunks and work). */
 typedef struct bssl_amd_iov_batch_st {
   size_t num_records;
   const CRYPTO_IOVEC *iovecs;

@@ -39,7 +39,9 @@ typedef struct bssl_amd_tls_aead_st BSSL_AMD_TLS_AEAD;
  * ssl/ssl_cipher.cc).  fixed_iv: 4 bytes for TLS 1.2 AES-GCM, 12 otherwise.
  * `seq` is the sequence number of the first record (TLS 1.3 traffic keys
  * start at 0, which the tls13 AEAD's nonce check relies on, e_aes.cc.inc:
- * 1181-1185).  Returns NULL on error. */
+ * 1181-1185).  Returns NULL on error; any other AEAD (AES-GCM-SIV, XChaCha,
+ * AES-CCM, AES-EAX: the reference's TLS stack has no such suites) is rejected
+ * with CIPHER_R_UNSUPPORTED_KEY_SIZE. */
 BSSL_AMD_EXPORT BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(
     enum evp_aead_direction_t direction, uint16_t version, const EVP_AEAD *aead,
     const uint8_t *key, size_t key_len, const uint8_t *fixed_iv, size_t fixed_iv_len,

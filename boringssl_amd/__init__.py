@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "EVP_aead_aes_128_gcm_siv", "EVP_aead_aes_256_gcm_siv", "EVP_aead_aes_128_gcm_tls12", "EVP_aead_aes_256_gcm_tls12",
     "EVP_aead_aes_128_ccm_bluetooth", "EVP_aead_aes_128_ccm_bluetooth_8",
     "EVP_aead_aes_128_ccm_matter", "EVP_aead_aes_128_eax", "EVP_aead_aes_256_eax",
+    "EVP_aead_aes_128_ctr_hmac_sha256", "EVP_aead_aes_256_ctr_hmac_sha256",
     "EVP_aead_aes_128_gcm_tls13", "EVP_aead_aes_256_gcm_tls13",
     "EVP_AEAD_key_length", "EVP_AEAD_nonce_length", "EVP_AEAD_max_overhead",
     "EVP_AEAD_max_tag_len", "EVP_AEAD_CTX_zero", "EVP_AEAD_CTX_new", "EVP_AEAD_CTX_free",
@@ -202,6 +203,8 @@ AEADS = {
     "aes-128-ccm-matter": _lib.EVP_aead_aes_128_ccm_matter,
     "aes-128-eax": _lib.EVP_aead_aes_128_eax,
     "aes-256-eax": _lib.EVP_aead_aes_256_eax,
+    "aes-128-ctr-hmac-sha256": _lib.EVP_aead_aes_128_ctr_hmac_sha256,
+    "aes-256-ctr-hmac-sha256": _lib.EVP_aead_aes_256_ctr_hmac_sha256,
     "aes-128-gcm-tls12": _lib.EVP_aead_aes_128_gcm_tls12,
     "aes-256-gcm-tls12": _lib.EVP_aead_aes_256_gcm_tls12,
     "aes-128-gcm-tls13": _lib.EVP_aead_aes_128_gcm_tls13,

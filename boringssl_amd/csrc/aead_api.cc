@@ -88,6 +88,9 @@ const evp_aead_st kAes128CcmBluetooth8 = {16, 13, 8, 8, kAeadAesCcm, 0};
 const evp_aead_st kAes128CcmMatter = {16, 13, 16, 16, kAeadAesCcm, 0};
 const evp_aead_st kAes128Eax = {16, 16, 16, 16, kAeadAesEax, 0};
 const evp_aead_st kAes256Eax = {32, 16, 16, 16, kAeadAesEax, 0};
+// e_aesctrhmac.cc:256-286: AES key || 32-byte HMAC key, 32-byte tags.
+const evp_aead_st kAes128CtrHmacSha256 = {48, 12, 32, 32, kAeadAesCtrHmac, 0};
+const evp_aead_st kAes256CtrHmacSha256 = {64, 12, 32, 32, kAeadAesCtrHmac, 0};
 const evp_aead_st kAes128GcmTls12 = {16, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes256GcmTls12 = {32, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes128GcmTls13 = {16, 12, 16, 16, kAeadAesGcm, 13};
@@ -99,7 +102,9 @@ struct KeyMaterial {
   int device;  // the HIP device the key material lives on
   size_t num_keys;
   int nr;
-  void *dev;  // GcmKeyDev[num_keys], CbcKeyDev[num_keys] or ChaChaKeyDev[num_keys]
+  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], CtrHmacKeyDev[num_keys] or
+  // ChaChaKeyDev[num_keys]
+  void *dev;
   size_t bytes;
 };
 
@@ -143,6 +148,12 @@ CtxState *state_of(const EVP_AEAD_CTX *ctx) {
 
 bool is_cbcmac(const EVP_AEAD *aead) {
   return aead->kind == kAeadAesCcm || aead->kind == kAeadAesEax;
+}
+
+// The AEADs of the one-lane-per-record kernels (cbcmac.hip, ctr_hmac.hip):
+// host key setup, no one-record kernel, no iovec walk.
+bool is_lane_per_record(const EVP_AEAD *aead) {
+  return is_cbcmac(aead) || aead->kind == kAeadAesCtrHmac;
 }
 
 // Key material of num_keys keys on the current device.  AES-GCM(-SIV) key
@@ -201,6 +212,17 @@ KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_key
     CbcKeyDev *h = reinterpret_cast<CbcKeyDev *>(host.data());
     for (size_t i = 0; i < num_keys; i++) {
       if (!cbc_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
+        delete km;
+        return nullptr;
+      }
+    }
+    km->nr = (int)h[0].nr;
+  } else if (aead->kind == kAeadAesCtrHmac) {  // host key setup only, 320 B per key
+    bytes = num_keys * sizeof(CtrHmacKeyDev);
+    host.resize(bytes);
+    CtrHmacKeyDev *h = reinterpret_cast<CtrHmacKeyDev *>(host.data());
+    for (size_t i = 0; i < num_keys; i++) {
+      if (!ctr_hmac_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
         delete km;
         return nullptr;
       }
@@ -303,6 +325,9 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
     rc = launch_cbcmac(static_cast<const CbcKeyDev *>(km->dev), d, km->aead->kind == kAeadAesEax,
                        open, km->nr, stream, ev);
     t_timing.last_name = "cbcmac_kernel";
+  } else if (km->aead->kind == kAeadAesCtrHmac) {
+    rc = launch_ctr_hmac(static_cast<const CtrHmacKeyDev *>(km->dev), d, open, km->nr, stream, ev);
+    t_timing.last_name = "ctr_hmac_kernel";
   } else {
     rc = launch_chacha(static_cast<const ChaChaKeyDev *>(km->dev), d, open,
                        km->aead->kind == kAeadXChaChaPoly, stream, ev);
@@ -351,7 +376,7 @@ int run_batch(const KeyMaterial *km, size_t tag_len, const BSSL_AMD_BATCH *batch
     // (*done_armed tells one_record whether to spin on it).
     const AeadKind k = km->aead->kind;
     const bool writes = k == kAeadAesGcm ? gcm_takes_one_record_kernel(d, gcm_eng)
-                        : k == kAeadAesGcmSiv || is_cbcmac(km->aead) ? false
+                        : k == kAeadAesGcmSiv || is_lane_per_record(km->aead) ? false
                                               : chacha_takes_one_record_kernel(d);
     d.done = writes ? one->done : nullptr;
     if (done_armed) *done_armed = d.done != nullptr;
@@ -514,8 +539,8 @@ bool wait_record(hipStream_t s, const uint32_t *done, uint32_t seq) {
 
 // Seal or open one record held in host memory.  `in`/`out` may be equal.
 // For open, `tag` is read; for seal it is written (tag_len bytes).
-// Staging layout (device and pinned host alike): nonce | AD | tag, status
-// (32 B) | record -- one H2D copy of all of it, one D2H copy of tag, status
+// Staging layout (device and pinned host alike): nonce | AD | tag (32 B, the
+// longest: AES-CTR-HMAC-SHA256), status (16 B) | record -- one H2D copy of all of it, one D2H copy of tag, status
 // and record.
 int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *out,
                size_t len, const uint8_t *nonce, size_t nonce_len, const uint8_t *ad,
@@ -527,7 +552,7 @@ int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *o
     return 0;
   }
   const size_t o_nonce = 0, o_ad = round16(nonce_len), o_tag = o_ad + round16(ad_len),
-               o_status = o_tag + 16, o_in = o_status + 16, total = o_in + round16(len);
+               o_status = o_tag + 32, o_in = o_status + 16, total = o_in + round16(len);
   Scratch *sc = scratch(total);
   if (!sc) {
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
@@ -740,6 +765,13 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
       PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
       return false;
     }
+  } else if (aead->kind == kAeadAesCtrHmac) {
+    // e_aesctrhmac.cc:201-204, 237-240; the callers have checked the length
+    // (:190, 226) and, on open, the tag length (:232) before this.
+    if (nonce_len != 12) {
+      PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
+      return false;
+    }
   } else {
     if (nonce_len != aead->nonce_len) {  // 12, or 24 for XChaCha (e_chacha20poly1305.cc:241)
       PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
@@ -756,7 +788,7 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
 // The per-AEAD tag-length rule of init (e_aes.cc.inc:742-749,
 // e_chacha20poly1305.cc:51-57, e_aesgcmsiv.cc:542-548): 0 means the maximum.
 // CCM takes its M only (e_aesccm.cc.inc:287-294), EAX 16 only
-// (e_aeseax.cc:72-79).
+// (e_aeseax.cc:72-79); CTR-HMAC any length up to 32 (e_aesctrhmac.cc:93-100).
 bool resolve_tag_len(const EVP_AEAD *aead, size_t *tag_len) {
   if (*tag_len == EVP_AEAD_DEFAULT_TAG_LENGTH) *tag_len = aead->max_tag_len;
   if (is_cbcmac(aead)) {
@@ -765,8 +797,10 @@ bool resolve_tag_len(const EVP_AEAD *aead, size_t *tag_len) {
     return false;
   }
   if (*tag_len > aead->max_tag_len || (aead->kind == kAeadAesGcmSiv && *tag_len != 16)) {
-    PUT_ERROR(aead->kind == kAeadAesGcm || aead->kind == kAeadAesGcmSiv ? CIPHER_R_TAG_TOO_LARGE
-                                                                       : CIPHER_R_TOO_LARGE);
+    PUT_ERROR(aead->kind == kAeadAesGcm || aead->kind == kAeadAesGcmSiv ||
+                      aead->kind == kAeadAesCtrHmac
+                  ? CIPHER_R_TAG_TOO_LARGE
+                  : CIPHER_R_TOO_LARGE);
     return false;
   }
   return true;
@@ -790,6 +824,8 @@ const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth_8(void) { return &kAes128CcmBluet
 const EVP_AEAD *EVP_aead_aes_128_ccm_matter(void) { return &kAes128CcmMatter; }
 const EVP_AEAD *EVP_aead_aes_128_eax(void) { return &kAes128Eax; }
 const EVP_AEAD *EVP_aead_aes_256_eax(void) { return &kAes256Eax; }
+const EVP_AEAD *EVP_aead_aes_128_ctr_hmac_sha256(void) { return &kAes128CtrHmacSha256; }
+const EVP_AEAD *EVP_aead_aes_256_ctr_hmac_sha256(void) { return &kAes256CtrHmacSha256; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void) { return &kAes128GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void) { return &kAes256GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void) { return &kAes128GcmTls13; }
@@ -898,6 +934,10 @@ int EVP_AEAD_CTX_sealv(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iovec, size_
       PUT_ERROR(CIPHER_R_OUTPUT_ALIASES_INPUT);
       return 0;
     }
+  if (ctx->aead->kind == kAeadAesCtrHmac && (uint64_t)total > kCtrHmacMaxInput) {
+    PUT_ERROR(CIPHER_R_TOO_LARGE);  // before the tag buffer, e_aesctrhmac.cc:190-199
+    return 0;
+  }
   if (max_out_tag_len < ctx->tag_len) {  // e_aes.cc.inc:785-788
     PUT_ERROR(CIPHER_R_BUFFER_TOO_SMALL);
     return 0;
@@ -909,7 +949,8 @@ int EVP_AEAD_CTX_sealv(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iovec, size_
   }
   std::vector<uint8_t> in = gather_in(iovec, num_iovec, total);
   std::vector<uint8_t> ad = gather_ad(aadvec, num_aadvec, ad_total);
-  uint8_t tag[16];
+  uint8_t tag[EVP_AEAD_MAX_OVERHEAD];  // the longest tag is CTR-HMAC's 32 bytes
+  static_assert(sizeof(tag) >= 32, "tag buffer");
   if (!one_record(ctx, false, in.data(), in.data(), total, nonce, nonce_len, ad.data(),
                   ad_total, tag, ctx->tag_len))
     return 0;
@@ -959,6 +1000,12 @@ int EVP_AEAD_CTX_openv_detached(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iov
   } else if (ctx->aead->kind == kAeadAesEax && in_tag_len != ctx->tag_len) {
     PUT_ERROR(CIPHER_R_BAD_DECRYPT);  // before the nonce check, e_aeseax.cc:276-284
     return 0;
+  } else if (ctx->aead->kind == kAeadAesCtrHmac &&
+             ((uint64_t)total > kCtrHmacMaxInput || in_tag_len != ctx->tag_len)) {
+    // The length, then the tag length, both before the nonce check
+    // (e_aesctrhmac.cc:226-240).
+    PUT_ERROR(CIPHER_R_BAD_DECRYPT);
+    return 0;
   } else if (!aead_record_checks(ctx, nonce_len, total)) {
     return 0;
   }
@@ -968,7 +1015,7 @@ int EVP_AEAD_CTX_openv_detached(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iov
   }
   std::vector<uint8_t> in = gather_in(iovec, num_iovec, total);
   std::vector<uint8_t> ad = gather_ad(aadvec, num_aadvec, ad_total);
-  uint8_t tag[16];
+  uint8_t tag[EVP_AEAD_MAX_OVERHEAD];  // in_tag_len == ctx->tag_len <= 32
   memcpy(tag, in_tag, in_tag_len);
   if (!one_record(ctx, true, in.data(), in.data(), total, nonce, nonce_len, ad.data(),
                   ad_total, tag, in_tag_len))
@@ -1289,7 +1336,7 @@ IovBatchDesc iov_desc(const BSSL_AMD_IOV_BATCH *b) {
 int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_BATCH *batch,
                                     void *hip_stream) {
   if (!ctx || !ctx->aead) return 0;
-  if (is_cbcmac(ctx->aead)) {  // no iovec walk in cbcmac.hip: nothing is launched
+  if (is_lane_per_record(ctx->aead)) {  // no iovec walk in their kernels: nothing is launched
     PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
     return 0;
   }
@@ -1331,7 +1378,7 @@ int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_
 int EVP_AEAD_CTX_openv_detached_batch_device(const EVP_AEAD_CTX *ctx,
                                              const BSSL_AMD_IOV_BATCH *batch, void *hip_stream) {
   if (!ctx || !ctx->aead) return 0;
-  if (is_cbcmac(ctx->aead)) {
+  if (is_lane_per_record(ctx->aead)) {
     PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
     return 0;
   }
@@ -1622,6 +1669,10 @@ BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(enum evp_aead_direction_t direction, ui
     return nullptr;
   }
   const bool tls13 = version == BSSL_AMD_TLS1_3_VERSION;
+  if (aead->kind == kAeadAesCtrHmac) {  // no record layer for it here (tls.h)
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
+    return nullptr;
+  }
   const EVP_AEAD *rec_aead = tls_record_aead(aead, tls13);
   if (!rec_aead) {
     PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);

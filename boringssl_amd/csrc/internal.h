@@ -13,6 +13,8 @@
 //   ChaChaKeyDev one per ChaCha20-Poly1305 key (32 bytes).
 //   CbcKeyDev   one per AES-CCM / AES-EAX key (336 bytes): the plain round
 //               keys and EAX's per-key constants (cbcmac.hip).
+//   CtrHmacKeyDev one per AES-CTR-HMAC-SHA256 key (320 bytes): the plain round
+//               keys and HMAC's inner and outer SHA-256 states (ctr_hmac.hip).
 //   BatchDesc   the record-batch descriptor passed by value to the kernels.
 #ifndef BSSL_AMD_INTERNAL_H
 #define BSSL_AMD_INTERNAL_H
@@ -76,13 +78,28 @@ struct alignas(16) CbcKeyDev {
 };
 static_assert(sizeof(CbcKeyDev) == 240 + 16 + 32 + 48, "layout");
 
+// One per AES-128/256-CTR-HMAC-SHA256 key (320 bytes; ctr_hmac.hip): the
+// FIPS-197 schedule of the AES half of the key as little-endian words,
+// unrotated, and the SHA-256 states of hmac_init
+// (crypto/cipher/e_aesctrhmac.cc:52-74) after the block (HMAC key || 0^32) XOR
+// 0x36.. (inner) and XOR 0x5c.. (outer), as FIPS 180-4's words H0..H7.
+struct alignas(16) CtrHmacKeyDev {
+  uint32_t rk[15][4];
+  uint32_t nr;
+  uint32_t pad[3];
+  uint32_t inner[8];
+  uint32_t outer[8];
+};
+static_assert(sizeof(CtrHmacKeyDev) == 240 + 16 + 32 + 32, "layout");
+
 enum AeadKind : int {
   kAeadAesGcm = 0,
   kAeadChaChaPoly = 1,
   kAeadXChaChaPoly = 2,
   kAeadAesGcmSiv = 3,
   kAeadAesCcm = 4,
-  kAeadAesEax = 5
+  kAeadAesEax = 5,
+  kAeadAesCtrHmac = 6
 };
 
 // Device chunk descriptors of iovec records: CRYPTO_IOVEC / CRYPTO_IVEC
@@ -246,6 +263,13 @@ int launch_gcm_siv(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr,
 // written.
 int launch_cbcmac(const CbcKeyDev *keys, const BatchDesc &b, bool eax, bool open, int nr,
                   void *stream, const KernelEvents *ev);
+// AES-128/256-CTR-HMAC-SHA256 (ctr_hmac.hip), one lane per record; tag_len 1
+// to 32.  BatchDesc::extra and ::iovecs are not supported (error 1); ::done is
+// never written.
+int launch_ctr_hmac(const CtrHmacKeyDev *keys, const BatchDesc &b, bool open, int nr, void *stream,
+                    const KernelEvents *ev);
+// Its message limit: the 32-bit block counter (e_aesctrhmac.cc:190, 226).
+constexpr uint64_t kCtrHmacMaxInput = (uint64_t(1) << 36) - 1;
 // CCM's message limit with L = 2 (CRYPTO_ccm128_max_input).
 constexpr uint64_t kCcmMaxInput = 65535;
 // xchacha: XChaCha20-Poly1305 (24-byte nonces, per-record HChaCha20 subkey).
@@ -333,6 +357,9 @@ int gcm_key_setup_device(const uint8_t *keys, size_t key_len, size_t n, GcmKeyDe
 void chacha_key_setup(const uint8_t *key, ChaChaKeyDev *out);
 // AES-CCM / AES-EAX key (host only); false for a bad key length.
 bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out);
+// AES-CTR-HMAC-SHA256 key, AES key || 32-byte HMAC key (host only); false for
+// a bad key length.
+bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out);
 // Key counts from which make_keys builds AES-GCM tables on the device.
 constexpr size_t kDeviceKeySetupMin = 64;
 

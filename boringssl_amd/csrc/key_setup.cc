@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "key_sched.h"
+#include "sha256_k.h"
 
 namespace bssl_amd {
 
@@ -60,6 +61,67 @@ bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out) {
   }
   secure_zero(rk, sizeof(rk));
   secure_zero(l, sizeof(l));
+  return true;
+}
+
+namespace {
+
+// FIPS 180-4 6.2.2: one SHA-256 compression of the 64-byte block `blk` into
+// the state h.  Plain and slow: it runs twice per key.
+void sha256_block(uint32_t h[8], const uint8_t blk[64]) {
+  uint32_t w[64];
+  auto rotr = [](uint32_t x, int s) { return (x >> s) | (x << (32 - s)); };
+  for (int t = 0; t < 16; t++)
+    w[t] = (uint32_t)blk[4 * t] << 24 | (uint32_t)blk[4 * t + 1] << 16 |
+           (uint32_t)blk[4 * t + 2] << 8 | blk[4 * t + 3];
+  for (int t = 16; t < 64; t++) {
+    const uint32_t s0 = rotr(w[t - 15], 7) ^ rotr(w[t - 15], 18) ^ (w[t - 15] >> 3);
+    const uint32_t s1 = rotr(w[t - 2], 17) ^ rotr(w[t - 2], 19) ^ (w[t - 2] >> 10);
+    w[t] = w[t - 16] + s0 + w[t - 7] + s1;
+  }
+  uint32_t v[8];
+  for (int i = 0; i < 8; i++) v[i] = h[i];
+  for (int t = 0; t < 64; t++) {
+    const uint32_t a = v[0], e = v[4];
+    const uint32_t t1 = v[7] + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) +
+                        ((e & v[5]) ^ (~e & v[6])) + kSha256K[t] + w[t];
+    const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) +
+                        ((a & v[1]) ^ (a & v[2]) ^ (v[1] & v[2]));
+    for (int i = 7; i > 0; i--) v[i] = v[i - 1];
+    v[4] += t1;
+    v[0] = t1 + t2;
+  }
+  for (int i = 0; i < 8; i++) h[i] += v[i];
+  secure_zero(w, sizeof(w));
+  secure_zero(v, sizeof(v));
+}
+
+}  // namespace
+
+// aead_aes_ctr_hmac_sha256_init (crypto/cipher/e_aesctrhmac.cc:76-109): the
+// schedule of the AES key and hmac_init's two states (:52-74), each one
+// compression from SHA-256's initial value (FIPS 180-4 5.3.3) over the HMAC
+// key XOR the pad byte, the rest of the block the pad byte itself.
+bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out) {
+  if (key_len != 48 && key_len != 64) return false;
+  const size_t aes_len = key_len - 32;
+  uint32_t rk[60];
+  const int nr = ks_expand(key, (int)aes_len, rk);
+  if (!nr) return false;
+  memset(out, 0, sizeof(*out));
+  for (int r = 0; r <= nr; r++)
+    for (int c = 0; c < 4; c++) out->rk[r][c] = rk[4 * r + c];
+  out->nr = (uint32_t)nr;
+  uint8_t blk[64];
+  for (int pass = 0; pass < 2; pass++) {
+    const uint8_t pad = pass ? 0x5c : 0x36;
+    for (int i = 0; i < 64; i++) blk[i] = (uint8_t)((i < 32 ? key[aes_len + i] : 0) ^ pad);
+    uint32_t *h = pass ? out->outer : out->inner;
+    for (int i = 0; i < 8; i++) h[i] = kSha256Init[i];
+    sha256_block(h, blk);
+  }
+  secure_zero(blk, sizeof(blk));
+  secure_zero(rk, sizeof(rk));
   return true;
 }
 

@@ -92,6 +92,25 @@ BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ccm_bluetooth_8(void); /* aead.
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ccm_matter(void);      /* aead.h:183 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_eax(void);             /* aead.h:192 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_eax(void);             /* aead.h:197 */
+/* AES-128/256-CTR-HMAC-SHA256, the reference's encrypt-then-MAC AEAD
+ * (e_aesctrhmac.cc).  The key is the AES key (16 or 32 bytes) followed by a
+ * 32-byte HMAC key: 48 or 64 bytes; nonces are 12 bytes; overhead and longest
+ * tag 32.  The ciphertext is AES-CTR from the counter block nonce || be32(0);
+ * the tag is HMAC-SHA256 over le64(ad_len) || le64(msg_len) || nonce || ad ||
+ * zeros to a multiple of 64 || ciphertext, cut to the context's tag length.
+ * Rules as in the reference: tag_len 0 means 32 and any tag_len up to 32 is
+ * taken (a shorter tag is a prefix of the full one), a longer one fails init
+ * with CIPHER_R_TAG_TOO_LARGE, another key length with
+ * CIPHER_R_UNSUPPORTED_KEY_SIZE; per call, a message of 2^36 bytes or more is
+ * CIPHER_R_TOO_LARGE on seal and CIPHER_R_BAD_DECRYPT on open, a tag buffer
+ * below the tag length CIPHER_R_BUFFER_TOO_SMALL, a tag of another length
+ * CIPHER_R_BAD_DECRYPT (checked before the nonce, e_aesctrhmac.cc:226-240),
+ * a nonce of another length CIPHER_R_UNSUPPORTED_NONCE_SIZE.  They work with
+ * every host call, the contiguous device batches and keysets below (48- or
+ * 64-byte keys); the iovec device batches and the TLS record layer (tls.h)
+ * reject them with CIPHER_R_CTRL_NOT_IMPLEMENTED. */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ctr_hmac_sha256(void); /* aead.h:135 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_ctr_hmac_sha256(void); /* aead.h:139 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void);  /* aead.h:583 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void);  /* aead.h:584 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void);  /* aead.h:585 */
@@ -206,7 +225,8 @@ BSSL_AMD_EXPORT void ERR_clear_error(void);
  * (optional) receives 1 on success, 0 on failure (authentication failure on
  * open, or a per-record limit exceeded: GCM 2^36-32 bytes gcm.cc.inc:409,
  * ChaCha20-Poly1305 2^38-64 bytes e_chacha20poly1305.cc:138, AES-CCM 65535
- * bytes e_aesccm.cc.inc:320); a failed
+ * bytes e_aesccm.cc.inc:320, AES-CTR-HMAC 2^36-1 bytes e_aesctrhmac.cc:190);
+ * a failed
  * record's output (and, for seal, tag) is zero-filled, as the reference does
  * for a failed single call (aead.cc.inc:132-139, 539-547). */
 typedef struct bssl_amd_batch_st {
@@ -266,7 +286,7 @@ BSSL_AMD_EXPORT int EVP_AEAD_CTX_open_batch_device(const EVP_AEAD_CTX *ctx,
  * `hip_stream` (one small kernel for the per-record totals, then the bulk
  * kernels) and never synchronises it.  Chunks of one batch must not partially
  * overlap (aead.cc.inc:281-308; not checked on the device).
- * Not implemented for the AES-CCM and AES-EAX contexts: both calls return 0
+ * Not implemented for the AES-CCM, AES-EAX and AES-CTR-HMAC contexts: both calls return 0
  * with CIPHER_R_CTRL_NOT_IMPLEMENTED and launch nothing (their host sealv /
  * openv calls gather the chunks and work). */
 typedef struct bssl_amd_iov_batch_st {

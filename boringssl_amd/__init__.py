@@ -40,8 +40,10 @@ CIPHER_R_BAD_DECRYPT = 101
 CIPHER_R_BAD_KEY_LENGTH = 102
 CIPHER_R_BUFFER_TOO_SMALL = 103
 CIPHER_R_CTRL_NOT_IMPLEMENTED = 104
+CIPHER_R_INVALID_AD_SIZE = 109
 CIPHER_R_INVALID_NONCE_SIZE = 111
 CIPHER_R_INVALID_OPERATION = 112
+CIPHER_R_NO_DIRECTION_SET = 124
 CIPHER_R_OUTPUT_ALIASES_INPUT = 115
 CIPHER_R_TAG_TOO_LARGE = 116
 CIPHER_R_TOO_LARGE = 117
@@ -61,6 +63,8 @@ EXPORTED_SYMBOLS = [
     "EVP_aead_aes_128_ccm_bluetooth", "EVP_aead_aes_128_ccm_bluetooth_8",
     "EVP_aead_aes_128_ccm_matter", "EVP_aead_aes_128_eax", "EVP_aead_aes_256_eax",
     "EVP_aead_aes_128_ctr_hmac_sha256", "EVP_aead_aes_256_ctr_hmac_sha256",
+    "EVP_aead_aes_128_cbc_sha1_tls", "EVP_aead_aes_256_cbc_sha1_tls",
+    "EVP_aead_aes_128_cbc_sha256_tls",
     "EVP_aead_aes_128_gcm_tls13", "EVP_aead_aes_256_gcm_tls13",
     "EVP_AEAD_key_length", "EVP_AEAD_nonce_length", "EVP_AEAD_max_overhead",
     "EVP_AEAD_max_tag_len", "EVP_AEAD_CTX_zero", "EVP_AEAD_CTX_new", "EVP_AEAD_CTX_free",
@@ -71,7 +75,7 @@ EXPORTED_SYMBOLS = [
     "ERR_get_error", "ERR_peek_error", "ERR_peek_last_error", "ERR_clear_error",
     "EVP_AEAD_CTX_seal_batch_device", "EVP_AEAD_CTX_open_batch_device",
     "EVP_AEAD_CTX_sealv_batch_device", "EVP_AEAD_CTX_openv_detached_batch_device",
-    "BSSL_AMD_KEYSET_new", "BSSL_AMD_KEYSET_free", "BSSL_AMD_KEYSET_num_keys",
+    "BSSL_AMD_KEYSET_new", "BSSL_AMD_KEYSET_new_with_direction", "BSSL_AMD_KEYSET_free", "BSSL_AMD_KEYSET_num_keys",
     "BSSL_AMD_KEYSET_seal_batch_device", "BSSL_AMD_KEYSET_open_batch_device",
     "BSSL_AMD_set_device", "BSSL_AMD_device_count", "BSSL_AMD_synth_fill_device",
     "BSSL_AMD_set_kernel_timing", "BSSL_AMD_collect_kernel_times", "BSSL_AMD_last_kernel_ms",
@@ -106,7 +110,7 @@ class BSSL_AMD_BATCH(ctypes.Structure):
         ("record_stride", ctypes.c_uint64), ("record_len", ctypes.c_uint64),
         ("nonces", _P), ("nonce_len", _S), ("ad", _P), ("ad_offsets", _P), ("ad_lengths", _P),
         ("ad_stride", ctypes.c_uint64), ("ad_len", ctypes.c_uint64), ("tags", _P),
-        ("status", _P), ("key_index", _P),
+        ("status", _P), ("key_index", _P), ("out_lengths", _P),
     ]
 
 
@@ -157,6 +161,7 @@ _SIGS = {
     "EVP_AEAD_CTX_openv_detached_batch_device": (_I, [_CTXP, ctypes.POINTER(BSSL_AMD_IOV_BATCH),
                                                       _P]),
     "BSSL_AMD_KEYSET_new": (_P, [_P, _P, _S, _S]),
+    "BSSL_AMD_KEYSET_new_with_direction": (_P, [_P, _P, _S, _S, _I]),
     "BSSL_AMD_KEYSET_free": (None, [_P]),
     "BSSL_AMD_KEYSET_num_keys": (_S, [_P]),
     "BSSL_AMD_KEYSET_seal_batch_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_BATCH), _P]),
@@ -205,6 +210,9 @@ AEADS = {
     "aes-256-eax": _lib.EVP_aead_aes_256_eax,
     "aes-128-ctr-hmac-sha256": _lib.EVP_aead_aes_128_ctr_hmac_sha256,
     "aes-256-ctr-hmac-sha256": _lib.EVP_aead_aes_256_ctr_hmac_sha256,
+    "aes-128-cbc-sha1-tls": _lib.EVP_aead_aes_128_cbc_sha1_tls,
+    "aes-256-cbc-sha1-tls": _lib.EVP_aead_aes_256_cbc_sha1_tls,
+    "aes-128-cbc-sha256-tls": _lib.EVP_aead_aes_128_cbc_sha256_tls,
     "aes-128-gcm-tls12": _lib.EVP_aead_aes_128_gcm_tls12,
     "aes-256-gcm-tls12": _lib.EVP_aead_aes_256_gcm_tls12,
     "aes-128-gcm-tls13": _lib.EVP_aead_aes_128_gcm_tls13,
@@ -265,6 +273,16 @@ class AEADCtx:
     def tag_len(self):
         return self.ctx.tag_len
 
+    def tag_len_for(self, in_len, extra_in_len=0):
+        """EVP_AEAD_CTX_tag_len: the tag of a record of in_len (+ extra_in_len)
+        bytes -- the context's tag length, or for the TLS AES-CBC-HMAC AEADs
+        (whose own tag_len is 0) the MAC and that record's padding."""
+        n = _S(0)
+        if not _lib.EVP_AEAD_CTX_tag_len(ctypes.byref(self.ctx), ctypes.byref(n), in_len,
+                                         extra_in_len):
+            _fail("EVP_AEAD_CTX_tag_len")
+        return n.value
+
     def close(self):
         if self.ctx is not None:
             _lib.EVP_AEAD_CTX_cleanup(ctypes.byref(self.ctx))
@@ -322,11 +340,15 @@ class AEADCtx:
 class Keyset:
     """BSSL_AMD_KEYSET: many keys of one AEAD resident on the device."""
 
-    def __init__(self, aead, keys, num_keys, tag_len=EVP_AEAD_DEFAULT_TAG_LENGTH):
+    def __init__(self, aead, keys, num_keys, tag_len=EVP_AEAD_DEFAULT_TAG_LENGTH, direction=None):
         if isinstance(aead, str):
             aead = EVP_aead(aead)
         keys = bytes(keys)
-        self.h = _lib.BSSL_AMD_KEYSET_new(aead, keys, num_keys, tag_len)
+        if direction is None:
+            self.h = _lib.BSSL_AMD_KEYSET_new(aead, keys, num_keys, tag_len)
+        else:
+            self.h = _lib.BSSL_AMD_KEYSET_new_with_direction(aead, keys, num_keys, tag_len,
+                                                             direction)
         if not self.h:
             _fail("BSSL_AMD_KEYSET_new")
 
@@ -429,7 +451,7 @@ def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, len
 
 def make_batch(num_records, inp, out, tags, nonces, nonce_len, ad=None, *, offsets=None,
                lengths=None, record_stride=0, record_len=0, ad_offsets=None, ad_lengths=None,
-               ad_stride=0, ad_len=0, status=None, key_index=None):
+               ad_stride=0, ad_len=0, status=None, key_index=None, out_lengths=None):
     """Builds a BSSL_AMD_BATCH from torch device tensors (uint8 / int64 /
     int32).  The returned structure keeps references to the tensors."""
     b = BSSL_AMD_BATCH()
@@ -450,8 +472,10 @@ def make_batch(num_records, inp, out, tags, nonces, nonce_len, ad=None, *, offse
     b.tags = _dptr(tags)
     b.status = _dptr(status)
     b.key_index = _dptr(key_index)
+    b.out_lengths = _dptr(out_lengths)
+    # (key_index stays last: callers read it back as _refs[-1])
     b._refs = (inp, out, tags, nonces, ad, offsets, lengths, ad_offsets, ad_lengths, status,
-               key_index)
+               out_lengths, key_index)
     return b
 
 

@@ -91,6 +91,12 @@ const evp_aead_st kAes256Eax = {32, 16, 16, 16, kAeadAesEax, 0};
 // e_aesctrhmac.cc:256-286: AES key || 32-byte HMAC key, 32-byte tags.
 const evp_aead_st kAes128CtrHmacSha256 = {48, 12, 32, 32, kAeadAesCtrHmac, 0};
 const evp_aead_st kAes256CtrHmacSha256 = {64, 12, 32, 32, kAeadAesCtrHmac, 0};
+// e_tls.cc:412-447, 517-590: MAC key || AES key, the CBC IV as the nonce, the
+// overhead the MAC and the longest padding; max_tag_len is the MAC size (20:
+// HMAC-SHA1, 32: HMAC-SHA256).
+const evp_aead_st kAes128CbcSha1Tls = {36, 16, 36, 20, kAeadTlsCbc, 0};
+const evp_aead_st kAes256CbcSha1Tls = {52, 16, 36, 20, kAeadTlsCbc, 0};
+const evp_aead_st kAes128CbcSha256Tls = {48, 16, 48, 32, kAeadTlsCbc, 0};
 const evp_aead_st kAes128GcmTls12 = {16, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes256GcmTls12 = {32, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes128GcmTls13 = {16, 12, 16, 16, kAeadAesGcm, 13};
@@ -102,10 +108,12 @@ struct KeyMaterial {
   int device;  // the HIP device the key material lives on
   size_t num_keys;
   int nr;
-  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], CtrHmacKeyDev[num_keys] or
-  // ChaChaKeyDev[num_keys]
+  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], CtrHmacKeyDev[num_keys],
+  // TlsCbcKeyDev[num_keys] or ChaChaKeyDev[num_keys]
   void *dev;
   size_t bytes;
+  // kAeadTlsCbc: the one direction the keys work in (e_tls.cc:125-129, 274-278).
+  bool open_only = false;
 };
 
 // Makes `dev` the calling thread's current HIP device for the guard's scope
@@ -153,7 +161,21 @@ bool is_cbcmac(const EVP_AEAD *aead) {
 // The AEADs of the one-lane-per-record kernels (cbcmac.hip, ctr_hmac.hip):
 // host key setup, no one-record kernel, no iovec walk.
 bool is_lane_per_record(const EVP_AEAD *aead) {
-  return is_cbcmac(aead) || aead->kind == kAeadAesCtrHmac;
+  return is_cbcmac(aead) || aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc;
+}
+
+// kAeadTlsCbc: the MAC size, and the tag of a record (e_tls.cc:105-116).
+size_t tls_cbc_mac_len(const EVP_AEAD *aead) { return aead->max_tag_len; }
+size_t tls_cbc_tag_len(const EVP_AEAD *aead, size_t in_len) {
+  const size_t mac_len = tls_cbc_mac_len(aead);
+  return mac_len + 16 - ((in_len + mac_len) & 15);
+}
+
+// A TLS AEAD works in one direction only.
+bool tls_cbc_direction_ok(const KeyMaterial *km, bool open) {
+  if (km->aead->kind != kAeadTlsCbc || km->open_only == open) return true;
+  PUT_ERROR(CIPHER_R_INVALID_OPERATION);
+  return false;
 }
 
 // Key material of num_keys keys on the current device.  AES-GCM(-SIV) key
@@ -163,11 +185,12 @@ bool is_lane_per_record(const EVP_AEAD *aead) {
 // and synchronisation cost more than the host's few microseconds per key).
 // device_setup: -1 by that rule, 0 host, 1 device (BSSL_AMD_gcm_key_tables).
 KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_keys,
-                       int device_setup = -1) {
+                       int device_setup = -1, bool open_only = false) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
   KeyMaterial *km = new (std::nothrow) KeyMaterial{aead, dev, num_keys, 0, nullptr, 0};
   if (!km) return nullptr;
+  km->open_only = open_only;
   const bool gcm = aead->kind == kAeadAesGcm || aead->kind == kAeadAesGcmSiv;
   if (gcm && num_keys && (device_setup == 1 || (device_setup < 0 && num_keys >= kDeviceKeySetupMin))) {
     const size_t bytes = num_keys * sizeof(GcmKeyDev);
@@ -223,6 +246,18 @@ KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_key
     CtrHmacKeyDev *h = reinterpret_cast<CtrHmacKeyDev *>(host.data());
     for (size_t i = 0; i < num_keys; i++) {
       if (!ctr_hmac_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
+        delete km;
+        return nullptr;
+      }
+    }
+    km->nr = (int)h[0].nr;
+  } else if (aead->kind == kAeadTlsCbc) {  // host key setup only, 320 B per key
+    bytes = num_keys * sizeof(TlsCbcKeyDev);
+    host.resize(bytes);
+    TlsCbcKeyDev *h = reinterpret_cast<TlsCbcKeyDev *>(host.data());
+    for (size_t i = 0; i < num_keys; i++) {
+      if (!tls_cbc_key_setup(keys + i * aead->key_len, aead->key_len, tls_cbc_mac_len(aead),
+                             open_only, &h[i])) {
         delete km;
         return nullptr;
       }
@@ -328,6 +363,10 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
   } else if (km->aead->kind == kAeadAesCtrHmac) {
     rc = launch_ctr_hmac(static_cast<const CtrHmacKeyDev *>(km->dev), d, open, km->nr, stream, ev);
     t_timing.last_name = "ctr_hmac_kernel";
+  } else if (km->aead->kind == kAeadTlsCbc) {
+    rc = launch_tls_cbc(static_cast<const TlsCbcKeyDev *>(km->dev), d, tls_cbc_mac_len(km->aead) == 20,
+                        open, km->nr, stream, ev);
+    t_timing.last_name = "tls_cbc_kernel";
   } else {
     rc = launch_chacha(static_cast<const ChaChaKeyDev *>(km->dev), d, open,
                        km->aead->kind == kAeadXChaChaPoly, stream, ev);
@@ -368,6 +407,10 @@ int run_batch(const KeyMaterial *km, size_t tag_len, const BSSL_AMD_BATCH *batch
   d.extra = nullptr;
   d.extra_out = nullptr;
   d.extra_len = d.extra_stride = d.extra_out_stride = d.tag_stride = 0;
+  if (km->aead->kind == kAeadTlsCbc) {  // tag slots of the overhead; open reports the lengths
+    d.tag_len = km->aead->overhead;
+    d.out_lengths = open ? batch->out_lengths : nullptr;
+  }
   // The AES-GCM engine is read once per batch: the completion-word decision
   // below and the launch must agree on it.
   const int gcm_eng = km->aead->kind == kAeadAesGcm ? gcm_engine() : -1;
@@ -392,17 +435,29 @@ int run_batch(const KeyMaterial *km, size_t tag_len, const BSSL_AMD_BATCH *batch
   return 1;
 }
 
-bool check_batch(const EVP_AEAD *aead, const BSSL_AMD_BATCH *b) {
+bool check_batch(const EVP_AEAD *aead, const BSSL_AMD_BATCH *b, bool open = false) {
   if (!b) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return false;
   }
   if (b->num_records == 0) return true;
-  if (!b->in || !b->out || !b->nonces || !b->tags || (!b->ad && (b->ad_lengths || b->ad_len))) {
+  // (The TLS CBC AEADs open whole wire fragments: no tags.)
+  const bool needs_tags = !(open && aead->kind == kAeadTlsCbc);
+  if (!b->in || !b->out || !b->nonces || (needs_tags && !b->tags) ||
+      (!b->ad && (b->ad_lengths || b->ad_len))) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return false;
   }
-  if (aead->kind == kAeadAesGcm) {
+  if (aead->kind == kAeadTlsCbc) {
+    if (b->nonce_len != 16) {  // e_tls.cc:137-140, 286-289
+      PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
+      return false;
+    }
+    if (!b->ad_lengths && b->ad_len != 11) {  // :142-146, 291-295
+      PUT_ERROR(CIPHER_R_INVALID_AD_SIZE);
+      return false;
+    }
+  } else if (aead->kind == kAeadAesGcm) {
     if (b->nonce_len == 0) {  // e_aes.cc.inc:790-793
       PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
       return false;
@@ -539,12 +594,14 @@ bool wait_record(hipStream_t s, const uint32_t *done, uint32_t seq) {
 
 // Seal or open one record held in host memory.  `in`/`out` may be equal.
 // For open, `tag` is read; for seal it is written (tag_len bytes).
-// Staging layout (device and pinned host alike): nonce | AD | tag (32 B, the
-// longest: AES-CTR-HMAC-SHA256), status (16 B) | record -- one H2D copy of all of it, one D2H copy of tag, status
-// and record.
+// Staging layout (device and pinned host alike): nonce | AD | tag (48 B, the
+// longest: the tag slot of AES-128-CBC-SHA256-TLS), status (16 B: the status
+// byte, the completion word at +4, a TLS CBC open's plaintext length at +8) |
+// record -- one H2D copy of all of it, one D2H copy of tag, status and record.
+// out_len (TLS CBC open only): receives the plaintext length.
 int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *out,
                size_t len, const uint8_t *nonce, size_t nonce_len, const uint8_t *ad,
-               size_t ad_len, uint8_t *tag, size_t tag_len) {
+               size_t ad_len, uint8_t *tag, size_t tag_len, size_t *out_len = nullptr) {
   CtxState *st = state_of(ctx);
   DeviceGuard guard(st->km->device);
   if (!guard.ok) {
@@ -552,7 +609,7 @@ int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *o
     return 0;
   }
   const size_t o_nonce = 0, o_ad = round16(nonce_len), o_tag = o_ad + round16(ad_len),
-               o_status = o_tag + 32, o_in = o_status + 16, total = o_in + round16(len);
+               o_status = o_tag + 48, o_in = o_status + 16, total = o_in + round16(len);
   Scratch *sc = scratch(total);
   if (!sc) {
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
@@ -585,6 +642,7 @@ int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *o
   b.ad_len = ad_len;
   b.tags = d + o_tag;
   b.status = d + o_status;
+  b.out_lengths = out_len ? reinterpret_cast<uint64_t *>(d + o_status + 8) : nullptr;
   // Completion word (mapped path): the one-record kernels write `seq` there
   // last (BatchDesc::done).
   static thread_local uint32_t t_seq = 0;
@@ -615,6 +673,11 @@ int one_record(const EVP_AEAD_CTX *ctx, bool open, const uint8_t *in, uint8_t *o
   }
   if (len) memcpy(out, h + o_in, len);
   if (!open && tag_len) memcpy(tag, h + o_tag, tag_len);
+  if (out_len) {
+    uint64_t n;
+    memcpy(&n, h + o_status + 8, sizeof(n));
+    *out_len = (size_t)n;
+  }
   if (!h[o_status]) {
     PUT_ERROR(open ? CIPHER_R_BAD_DECRYPT : CIPHER_R_TOO_LARGE);
     return 0;
@@ -765,6 +828,11 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
       PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
       return false;
     }
+  } else if (aead->kind == kAeadTlsCbc) {
+    if (nonce_len != 16) {  // e_tls.cc:137-140, 286-289
+      PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
+      return false;
+    }
   } else if (aead->kind == kAeadAesCtrHmac) {
     // e_aesctrhmac.cc:201-204, 237-240; the callers have checked the length
     // (:190, 226) and, on open, the tag length (:232) before this.
@@ -790,6 +858,16 @@ bool aead_record_checks(const EVP_AEAD_CTX *ctx, size_t nonce_len, size_t in_len
 // CCM takes its M only (e_aesccm.cc.inc:287-294), EAX 16 only
 // (e_aeseax.cc:72-79); CTR-HMAC any length up to 32 (e_aesctrhmac.cc:93-100).
 bool resolve_tag_len(const EVP_AEAD *aead, size_t *tag_len) {
+  if (aead->kind == kAeadTlsCbc) {
+    // e_tls.cc:65-68: 0 or the MAC size; the context's tag length stays 0, the
+    // overhead varies with the record (EVP_AEAD_CTX_tag_len).
+    if (*tag_len != EVP_AEAD_DEFAULT_TAG_LENGTH && *tag_len != tls_cbc_mac_len(aead)) {
+      PUT_ERROR(CIPHER_R_UNSUPPORTED_TAG_SIZE);
+      return false;
+    }
+    *tag_len = 0;
+    return true;
+  }
   if (*tag_len == EVP_AEAD_DEFAULT_TAG_LENGTH) *tag_len = aead->max_tag_len;
   if (is_cbcmac(aead)) {
     if (*tag_len == aead->max_tag_len) return true;
@@ -826,6 +904,9 @@ const EVP_AEAD *EVP_aead_aes_128_eax(void) { return &kAes128Eax; }
 const EVP_AEAD *EVP_aead_aes_256_eax(void) { return &kAes256Eax; }
 const EVP_AEAD *EVP_aead_aes_128_ctr_hmac_sha256(void) { return &kAes128CtrHmacSha256; }
 const EVP_AEAD *EVP_aead_aes_256_ctr_hmac_sha256(void) { return &kAes256CtrHmacSha256; }
+const EVP_AEAD *EVP_aead_aes_128_cbc_sha1_tls(void) { return &kAes128CbcSha1Tls; }
+const EVP_AEAD *EVP_aead_aes_256_cbc_sha1_tls(void) { return &kAes256CbcSha1Tls; }
+const EVP_AEAD *EVP_aead_aes_128_cbc_sha256_tls(void) { return &kAes128CbcSha256Tls; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void) { return &kAes128GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void) { return &kAes256GcmTls12; }
 const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void) { return &kAes128GcmTls13; }
@@ -858,13 +939,17 @@ void EVP_AEAD_CTX_free(EVP_AEAD_CTX *ctx) {
 int EVP_AEAD_CTX_init(EVP_AEAD_CTX *ctx, const EVP_AEAD *aead, const uint8_t *key,
                       size_t key_len, size_t tag_len, ENGINE *impl) {
   (void)impl;
+  if (aead->kind == kAeadTlsCbc) {  // aead.cc.inc:73-77: no direction-less init
+    PUT_ERROR(CIPHER_R_NO_DIRECTION_SET);
+    ctx->aead = nullptr;
+    return 0;
+  }
   return EVP_AEAD_CTX_init_with_direction(ctx, aead, key, key_len, tag_len, evp_aead_open);
 }
 
 int EVP_AEAD_CTX_init_with_direction(EVP_AEAD_CTX *ctx, const EVP_AEAD *aead,
                                      const uint8_t *key, size_t key_len, size_t tag_len,
                                      enum evp_aead_direction_t dir) {
-  (void)dir;
   // aead.cc.inc:82-106
   if (key_len != aead->key_len) {
     PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
@@ -875,7 +960,7 @@ int EVP_AEAD_CTX_init_with_direction(EVP_AEAD_CTX *ctx, const EVP_AEAD *aead,
     ctx->aead = nullptr;
     return 0;
   }
-  KeyMaterial *km = make_keys(aead, key, 1);
+  KeyMaterial *km = make_keys(aead, key, 1, -1, dir == evp_aead_open);
   if (!km) {
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
     ctx->aead = nullptr;
@@ -938,6 +1023,31 @@ int EVP_AEAD_CTX_sealv(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iovec, size_
     PUT_ERROR(CIPHER_R_TOO_LARGE);  // before the tag buffer, e_aesctrhmac.cc:190-199
     return 0;
   }
+  if (ctx->aead->kind == kAeadTlsCbc) {
+    // e_tls.cc:125-146: the direction, the tag buffer, the nonce, the AD.
+    if (!tls_cbc_direction_ok(state_of(ctx)->km, false)) return 0;
+    const size_t tag_len = tls_cbc_tag_len(ctx->aead, total);
+    if (max_out_tag_len < tag_len) {
+      PUT_ERROR(CIPHER_R_BUFFER_TOO_SMALL);
+      return 0;
+    }
+    if (!aead_record_checks(ctx, nonce_len, total)) return 0;
+    if (ad_total != 11) {
+      PUT_ERROR(CIPHER_R_INVALID_AD_SIZE);
+      return 0;
+    }
+    std::vector<uint8_t> in = gather_in(iovec, num_iovec, total);
+    std::vector<uint8_t> ad = gather_ad(aadvec, num_aadvec, ad_total);
+    uint8_t tag[EVP_AEAD_MAX_OVERHEAD];  // the tag slot: 36 or 48 bytes
+    if (!one_record(ctx, false, in.data(), in.data(), total, nonce, nonce_len, ad.data(),
+                    ad_total, tag, ctx->aead->overhead))
+      return 0;
+    scatter_out(iovec, num_iovec, in.data(), total);
+    memcpy(out_tag, tag, tag_len);
+    *out_tag_len = tag_len;
+    ok = true;
+    return 1;
+  }
   if (max_out_tag_len < ctx->tag_len) {  // e_aes.cc.inc:785-788
     PUT_ERROR(CIPHER_R_BUFFER_TOO_SMALL);
     return 0;
@@ -986,6 +1096,10 @@ int EVP_AEAD_CTX_openv_detached(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iov
   }
   if (!iovec_internal_alias_ok(iovec, num_iovec)) {
     PUT_ERROR(CIPHER_R_OUTPUT_ALIASES_INPUT);
+    return 0;
+  }
+  if (ctx->aead->kind == kAeadTlsCbc) {  // aead.cc.inc:567-575: openv only
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
     return 0;
   }
   if (ctx->aead->kind == kAeadAesGcm) {
@@ -1050,6 +1164,37 @@ int EVP_AEAD_CTX_openv(const EVP_AEAD_CTX *ctx, const CRYPTO_IOVEC *iovec, size_
   if (!iovec_internal_alias_ok(iovec, num_iovec)) {
     PUT_ERROR(CIPHER_R_OUTPUT_ALIASES_INPUT);
     return 0;
+  }
+  if (ctx->aead->kind == kAeadTlsCbc) {
+    // aead_tls_openv (e_tls.cc:268-410): the direction, the MAC's room, the
+    // nonce, the AD; then what the decryption rejects (:315-319,
+    // tls_cbc.cc:37-39).  The kernel does the rest; the iovecs get the whole
+    // decryption, as the reference leaves it.
+    if (!tls_cbc_direction_ok(state_of(ctx)->km, true)) return 0;
+    const size_t mac_len = tls_cbc_mac_len(ctx->aead);
+    if (total < mac_len) {
+      PUT_ERROR(CIPHER_R_BAD_DECRYPT);
+      return 0;
+    }
+    if (!aead_record_checks(ctx, nonce_len, total)) return 0;
+    if (ad_total != 11) {
+      PUT_ERROR(CIPHER_R_INVALID_AD_SIZE);
+      return 0;
+    }
+    if ((total & 15) != 0 || total < mac_len + 1) {
+      PUT_ERROR(CIPHER_R_BAD_DECRYPT);
+      return 0;
+    }
+    std::vector<uint8_t> in = gather_in(iovec, num_iovec, total);
+    std::vector<uint8_t> ad = gather_ad(aadvec, num_aadvec, ad_total);
+    size_t data_len = 0;
+    if (!one_record(ctx, true, in.data(), in.data(), total, nonce, nonce_len, ad.data(), ad_total,
+                    nullptr, 0, &data_len))
+      return 0;
+    scatter_out(iovec, num_iovec, in.data(), total);
+    *out_total_bytes = data_len;
+    ok = true;
+    return 1;
   }
   if (total < ctx->tag_len) {
     PUT_ERROR(CIPHER_R_BAD_DECRYPT);
@@ -1171,6 +1316,19 @@ int EVP_AEAD_CTX_open(const EVP_AEAD_CTX *ctx, uint8_t *out, size_t *out_len,
       }
     }
   } cleanup{ok, out, max_out_len, out_len};
+  if (ctx->aead->kind == kAeadTlsCbc) {
+    // aead.cc.inc:408-427: a variable tag length; the caller gives room for the
+    // whole decryption.
+    if (max_out_len < in_len) {
+      PUT_ERROR(CIPHER_R_BUFFER_TOO_SMALL);
+      return 0;
+    }
+    CRYPTO_IOVEC iov = {out, in, in_len};
+    CRYPTO_IVEC aiv = {ad, ad_len};
+    if (!EVP_AEAD_CTX_openv(ctx, &iov, 1, out_len, nonce, nonce_len, &aiv, 1)) return 0;
+    ok = true;
+    return 1;
+  }
   if (in_len < ctx->tag_len) {
     PUT_ERROR(CIPHER_R_BAD_DECRYPT);
     return 0;
@@ -1216,8 +1374,15 @@ int EVP_AEAD_CTX_open_gather(const EVP_AEAD_CTX *ctx, uint8_t *out, const uint8_
 // aead.cc.inc:598-619
 int EVP_AEAD_CTX_tag_len(const EVP_AEAD_CTX *ctx, size_t *out_tag_len, size_t in_len,
                          size_t extra_in_len) {
-  (void)in_len;
   size_t tag_len = ctx->tag_len;
+  if (ctx->aead->kind == kAeadTlsCbc) {  // aead.cc.inc:601-607, e_tls.cc:105-116
+    if (in_len + extra_in_len < in_len) {
+      PUT_ERROR(ERR_R_OVERFLOW);
+      *out_tag_len = 0;
+      return 0;
+    }
+    tag_len = tls_cbc_tag_len(ctx->aead, in_len + extra_in_len);
+  }
   if (extra_in_len + tag_len < extra_in_len) {
     PUT_ERROR(ERR_R_OVERFLOW);
     *out_tag_len = 0;
@@ -1240,7 +1405,9 @@ int EVP_AEAD_CTX_get_iv(const EVP_AEAD_CTX *ctx, const uint8_t **out_iv, size_t 
 
 int EVP_AEAD_CTX_seal_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_BATCH *batch,
                                    void *hip_stream) {
-  if (!ctx || !ctx->aead || !check_batch(ctx->aead, batch)) return 0;
+  if (!ctx || !ctx->aead || !tls_cbc_direction_ok(state_of(ctx)->km, false) ||
+      !check_batch(ctx->aead, batch))
+    return 0;
   if (batch->num_records == 0) return 1;
   CtxState *st = state_of(ctx);
   if (!on_key_device(st->km)) return 0;
@@ -1269,7 +1436,9 @@ int EVP_AEAD_CTX_seal_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_BATCH
 
 int EVP_AEAD_CTX_open_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_BATCH *batch,
                                    void *hip_stream) {
-  if (!ctx || !ctx->aead || !check_batch(ctx->aead, batch)) return 0;
+  if (!ctx || !ctx->aead || !tls_cbc_direction_ok(state_of(ctx)->km, true) ||
+      !check_batch(ctx->aead, batch, true))
+    return 0;
   if (batch->num_records == 0) return 1;
   if (!on_key_device(state_of(ctx)->km)) return 0;
   return run_batch(state_of(ctx)->km, ctx->tag_len, batch, true, false, hip_stream);
@@ -1400,14 +1569,35 @@ struct bssl_amd_keyset_st {
   size_t tag_len;
 };
 
+namespace {
+BSSL_AMD_KEYSET *keyset_new(const EVP_AEAD *aead, const uint8_t *keys, size_t num_keys,
+                            size_t tag_len, bool open_only);
+}
+
 BSSL_AMD_KEYSET *BSSL_AMD_KEYSET_new(const EVP_AEAD *aead, const uint8_t *keys,
                                      size_t num_keys, size_t tag_len) {
+  if (aead && aead->kind == kAeadTlsCbc) {  // as EVP_AEAD_CTX_init: no direction-less keys
+    PUT_ERROR(CIPHER_R_NO_DIRECTION_SET);
+    return nullptr;
+  }
+  return keyset_new(aead, keys, num_keys, tag_len, false);
+}
+
+BSSL_AMD_KEYSET *BSSL_AMD_KEYSET_new_with_direction(const EVP_AEAD *aead, const uint8_t *keys,
+                                                    size_t num_keys, size_t tag_len,
+                                                    enum evp_aead_direction_t dir) {
+  return keyset_new(aead, keys, num_keys, tag_len, dir == evp_aead_open);
+}
+
+namespace {
+BSSL_AMD_KEYSET *keyset_new(const EVP_AEAD *aead, const uint8_t *keys, size_t num_keys,
+                            size_t tag_len, bool open_only) {
   if (!aead || !keys || num_keys == 0 || num_keys > 0xfffffffeu) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return nullptr;
   }
   if (!resolve_tag_len(aead, &tag_len)) return nullptr;
-  KeyMaterial *km = make_keys(aead, keys, num_keys);
+  KeyMaterial *km = make_keys(aead, keys, num_keys, -1, open_only);
   if (!km) {
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
     return nullptr;
@@ -1416,6 +1606,7 @@ BSSL_AMD_KEYSET *BSSL_AMD_KEYSET_new(const EVP_AEAD *aead, const uint8_t *keys,
   if (!ks) free_keys(km);
   return ks;
 }
+}  // namespace
 
 void BSSL_AMD_KEYSET_free(BSSL_AMD_KEYSET *ks) {
   if (!ks) return;
@@ -1427,7 +1618,7 @@ size_t BSSL_AMD_KEYSET_num_keys(const BSSL_AMD_KEYSET *ks) { return ks ? ks->km-
 
 int BSSL_AMD_KEYSET_seal_batch_device(const BSSL_AMD_KEYSET *ks, const BSSL_AMD_BATCH *batch,
                                       void *hip_stream) {
-  if (!ks || !check_batch(ks->km->aead, batch)) return 0;
+  if (!ks || !tls_cbc_direction_ok(ks->km, false) || !check_batch(ks->km->aead, batch)) return 0;
   if (ks->km->aead->tls) {  // per-key nonce state: one EVP_AEAD_CTX per key instead
     PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
     return 0;
@@ -1439,7 +1630,8 @@ int BSSL_AMD_KEYSET_seal_batch_device(const BSSL_AMD_KEYSET *ks, const BSSL_AMD_
 
 int BSSL_AMD_KEYSET_open_batch_device(const BSSL_AMD_KEYSET *ks, const BSSL_AMD_BATCH *batch,
                                       void *hip_stream) {
-  if (!ks || !check_batch(ks->km->aead, batch)) return 0;
+  if (!ks || !tls_cbc_direction_ok(ks->km, true) || !check_batch(ks->km->aead, batch, true))
+    return 0;
   if (batch->num_records == 0) return 1;
   if (!on_key_device(ks->km)) return 0;
   return run_batch(ks->km, ks->tag_len, batch, true, true, hip_stream);
@@ -1669,7 +1861,7 @@ BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(enum evp_aead_direction_t direction, ui
     return nullptr;
   }
   const bool tls13 = version == BSSL_AMD_TLS1_3_VERSION;
-  if (aead->kind == kAeadAesCtrHmac) {  // no record layer for it here (tls.h)
+  if (aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc) {  // no record layer for them here (tls.h)
     PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
     return nullptr;
   }

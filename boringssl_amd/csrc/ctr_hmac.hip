@@ -20,8 +20,9 @@
 //   the hash: a step's body computes the next step's keystream before it
 //   compresses its own ciphertext, and the two are independent on seal and
 //   open alike.  The AES is LDS lookups, the compression VALU work.
-// * The compression keeps the state in 8 registers and the message schedule
-//   in a rolling window of 16, fully unrolled, the 64 constants literals.
+// * The compression (sha_compress.h) keeps the state in 8 registers and the
+//   message schedule in a rolling window of 16, fully unrolled, the 64
+//   constants literals.
 // * One key: the round keys and both HMAC states are wave-uniform (scalar
 //   loads).  Keysets: round keys in per-lane LDS slots with an odd stride in
 //   words (cbcmac.hip); the two states are read from global memory once each.
@@ -31,7 +32,7 @@
 #include "aes_tables.h"
 #include "internal.h"
 #include "rec_blocks.h"
-#include "sha256_k.h"
+#include "sha_compress.h"
 
 namespace bssl_amd {
 namespace {
@@ -59,55 +60,6 @@ static_assert(sizeof(Lds<10, true>) <= 160 * 1024 && sizeof(Lds<14, true>) <= 16
               "LDS per workgroup");
 static_assert(Shape<10, true>::kStride % 2 == 1 && Shape<14, true>::kStride % 2 == 1,
               "odd slot stride: lane l's word w in bank (l * stride + w) % 64, all different");
-
-// ---- SHA-256 (FIPS 180-4 4.1.2, 6.2.2) ----------------------------------------
-
-__device__ __forceinline__ uint32_t rotr(uint32_t v, int n) {
-  return __builtin_amdgcn_alignbit(v, v, n);
-}
-// Bits of x where m is set, of y elsewhere, and the XOR of three words: one
-// v_bitop3_b32 each (gfx950's three-input boolean, which takes v_bfi_b32's
-// place here).
-__device__ __forceinline__ uint32_t bfi(uint32_t m, uint32_t x, uint32_t y) {
-  return (m & x) | (~m & y);
-}
-__device__ __forceinline__ uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) {
-  return __builtin_amdgcn_bitop3_b32(x, y, z, 0x96);
-}
-
-// One compression: h += the 64 rounds over the block w (its sixteen big-endian
-// words; used up as the schedule's rolling window).
-__device__ __forceinline__ void sha256_compress(uint32_t (&h)[8], uint32_t (&w)[16]) {
-  uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-#pragma unroll
-  for (int t = 0; t < 64; t++) {
-    if (t >= 16) {
-      const uint32_t w15 = w[(t + 1) & 15], w2 = w[(t + 14) & 15];
-      w[t & 15] += xor3(rotr(w15, 7), rotr(w15, 18), w15 >> 3) + w[(t + 9) & 15] +
-                   xor3(rotr(w2, 17), rotr(w2, 19), w2 >> 10);
-    }
-    const uint32_t t1 = hh + xor3(rotr(e, 6), rotr(e, 11), rotr(e, 25)) + bfi(e, f, g) +
-                        kSha256K[t] + w[t & 15];
-    // Maj(a, b, c): c where a and b differ, else b.
-    const uint32_t t2 = xor3(rotr(a, 2), rotr(a, 13), rotr(a, 22)) + bfi(a ^ b, c, b);
-    hh = g; g = f; f = e; e = d + t1;
-    d = c; c = b; b = a; a = t1 + t2;
-  }
-  h[0] += a; h[1] += b; h[2] += c; h[3] += d;
-  h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-}
-
-// Four 16-byte blocks (little-endian words of their bytes) as the sixteen
-// big-endian words of a SHA-256 block.
-__device__ __forceinline__ void to_schedule(const uint4 (&v)[4], uint32_t (&w)[16]) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    w[4 * k] = __builtin_bswap32(v[k].x);
-    w[4 * k + 1] = __builtin_bswap32(v[k].y);
-    w[4 * k + 2] = __builtin_bswap32(v[k].z);
-    w[4 * k + 3] = __builtin_bswap32(v[k].w);
-  }
-}
 
 // min(16, the bytes of [0, total) from `at` on).
 __device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {

@@ -15,6 +15,9 @@
 //               keys and EAX's per-key constants (cbcmac.hip).
 //   CtrHmacKeyDev one per AES-CTR-HMAC-SHA256 key (320 bytes): the plain round
 //               keys and HMAC's inner and outer SHA-256 states (ctr_hmac.hip).
+//   TlsCbcKeyDev one per TLS AES-CBC-HMAC key (320 bytes): the round keys of
+//               the context's direction and HMAC's inner and outer SHA-1 or
+//               SHA-256 states (tls_cbc.hip).
 //   BatchDesc   the record-batch descriptor passed by value to the kernels.
 #ifndef BSSL_AMD_INTERNAL_H
 #define BSSL_AMD_INTERNAL_H
@@ -92,6 +95,22 @@ struct alignas(16) CtrHmacKeyDev {
 };
 static_assert(sizeof(CtrHmacKeyDev) == 240 + 16 + 32 + 32, "layout");
 
+// One per TLS AES-CBC-HMAC-SHA1/SHA256 key (320 bytes; tls_cbc.hip).  The key
+// is MAC key || AES key (e_tls.cc:75-96).  rk: for a sealing context the
+// FIPS-197 schedule as little-endian words; for an opening one the schedule of
+// the equivalent inverse cipher (FIPS-197 5.3.5: the round keys in reverse
+// order, InvMixColumns applied to rounds 1..nr-1).  inner / outer: HMAC's
+// states after the block (MAC key || zeros) XOR 0x36.. / 0x5c.., as FIPS
+// 180-4's words (SHA-1 uses the first five).
+struct alignas(16) TlsCbcKeyDev {
+  uint32_t rk[15][4];
+  uint32_t nr;
+  uint32_t pad[3];
+  uint32_t inner[8];
+  uint32_t outer[8];
+};
+static_assert(sizeof(TlsCbcKeyDev) == 240 + 16 + 32 + 32, "layout");
+
 enum AeadKind : int {
   kAeadAesGcm = 0,
   kAeadChaChaPoly = 1,
@@ -99,7 +118,8 @@ enum AeadKind : int {
   kAeadAesGcmSiv = 3,
   kAeadAesCcm = 4,
   kAeadAesEax = 5,
-  kAeadAesCtrHmac = 6
+  kAeadAesCtrHmac = 6,
+  kAeadTlsCbc = 7
 };
 
 // Device chunk descriptors of iovec records: CRYPTO_IOVEC / CRYPTO_IVEC
@@ -182,6 +202,9 @@ struct BatchDesc {
   uint32_t inl;
   uint32_t inl_nonce[3];
   uint32_t inl_ad[4];
+  // TLS AES-CBC-HMAC open only (BSSL_AMD_BATCH::out_lengths): record i's
+  // plaintext length goes here (0 for a failed record).  Null: not reported.
+  uint64_t *out_lengths;
 };
 
 // Tag / extra addresses of record i.
@@ -268,6 +291,15 @@ int launch_cbcmac(const CbcKeyDev *keys, const BatchDesc &b, bool eax, bool open
 // never written.
 int launch_ctr_hmac(const CtrHmacKeyDev *keys, const BatchDesc &b, bool open, int nr, void *stream,
                     const KernelEvents *ev);
+// The TLS AES-CBC-HMAC AEADs (tls_cbc.hip), one lane per record.  sha1: the
+// MAC is HMAC-SHA1 (20 bytes), else HMAC-SHA256 (32); tag_len is the tag slot
+// stride (the AEAD's overhead, 36 or 48).  Seal: `keys` hold encryption
+// schedules, the tag (MAC and padding, ciphertext) goes to the record's slot.
+// Open: `keys` hold equivalent-inverse schedules, the records are whole wire
+// fragments, `tags` is unused.  BatchDesc::extra and ::iovecs are not
+// supported (error 1); ::done is never written.
+int launch_tls_cbc(const TlsCbcKeyDev *keys, const BatchDesc &b, bool sha1, bool open, int nr,
+                   void *stream, const KernelEvents *ev);
 // Its message limit: the 32-bit block counter (e_aesctrhmac.cc:190, 226).
 constexpr uint64_t kCtrHmacMaxInput = (uint64_t(1) << 36) - 1;
 // CCM's message limit with L = 2 (CRYPTO_ccm128_max_input).
@@ -360,6 +392,11 @@ bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out);
 // AES-CTR-HMAC-SHA256 key, AES key || 32-byte HMAC key (host only); false for
 // a bad key length.
 bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out);
+// TLS AES-CBC-HMAC key, MAC key (mac_len: 20 or 32 bytes) || AES key (host
+// only); open: the schedule of the equivalent inverse cipher.  false for a bad
+// key length.
+bool tls_cbc_key_setup(const uint8_t *key, size_t key_len, size_t mac_len, bool open,
+                       TlsCbcKeyDev *out);
 // Key counts from which make_keys builds AES-GCM tables on the device.
 constexpr size_t kDeviceKeySetupMin = 64;
 

@@ -127,6 +127,80 @@ bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out) 
 
 namespace {
 
+// FIPS 180-4 6.1.2: one SHA-1 compression of the 64-byte block `blk` into the
+// state h.  Plain and slow, as sha256_block.
+void sha1_block(uint32_t h[5], const uint8_t blk[64]) {
+  uint32_t w[80];
+  auto rotl = [](uint32_t x, int s) { return (x << s) | (x >> (32 - s)); };
+  for (int t = 0; t < 16; t++)
+    w[t] = (uint32_t)blk[4 * t] << 24 | (uint32_t)blk[4 * t + 1] << 16 |
+           (uint32_t)blk[4 * t + 2] << 8 | blk[4 * t + 3];
+  for (int t = 16; t < 80; t++) w[t] = rotl(w[t - 3] ^ w[t - 8] ^ w[t - 14] ^ w[t - 16], 1);
+  uint32_t v[5];
+  for (int i = 0; i < 5; i++) v[i] = h[i];
+  for (int t = 0; t < 80; t++) {
+    const uint32_t b = v[1], c = v[2], d = v[3];
+    const uint32_t f = t < 20 ? (b & c) | (~b & d) : t < 40 ? b ^ c ^ d
+                       : t < 60 ? (b & c) | (b & d) | (c & d) : b ^ c ^ d;
+    const uint32_t k = t < 20 ? 0x5a827999u : t < 40 ? 0x6ed9eba1u
+                       : t < 60 ? 0x8f1bbcdcu : 0xca62c1d6u;
+    const uint32_t tmp = rotl(v[0], 5) + f + v[4] + k + w[t];
+    v[4] = d; v[3] = c; v[2] = rotl(b, 30); v[1] = v[0]; v[0] = tmp;
+  }
+  for (int i = 0; i < 5; i++) h[i] += v[i];
+  secure_zero(w, sizeof(w));
+  secure_zero(v, sizeof(v));
+}
+
+// InvMixColumns (FIPS-197 5.3.3) of one column, a little-endian word of its
+// four bytes: bytes i and i + 2 take 4 (a_i ^ a_{i+2}), then MixColumns.
+uint32_t inv_mix_column(uint32_t a) {
+  a ^= ks_xtime4(ks_xtime4(a ^ ks_rotr8(a, 2)));
+  const uint32_t a1 = ks_rotr8(a, 1);
+  return a1 ^ ks_rotr8(a, 2) ^ ks_rotr8(a, 3) ^ ks_xtime4(a ^ a1);
+}
+
+}  // namespace
+
+// aead_tls_init (crypto/cipher/e_tls.cc:61-103): the key is MAC key || AES key;
+// HMAC's two states as for ctr_hmac_key_setup, over SHA-1 (mac_len 20) or
+// SHA-256 (32).  An opening context decrypts: its schedule is the one of the
+// equivalent inverse cipher (FIPS-197 5.3.5).
+bool tls_cbc_key_setup(const uint8_t *key, size_t key_len, size_t mac_len, bool open,
+                       TlsCbcKeyDev *out) {
+  if ((mac_len != 20 && mac_len != 32) || key_len <= mac_len) return false;
+  uint32_t rk[60];
+  const int nr = ks_expand(key + mac_len, (int)(key_len - mac_len), rk);
+  if (!nr) return false;
+  memset(out, 0, sizeof(*out));
+  for (int r = 0; r <= nr; r++)
+    for (int c = 0; c < 4; c++) {
+      const uint32_t w = rk[4 * (open ? nr - r : r) + c];
+      out->rk[r][c] = open && r > 0 && r < nr ? inv_mix_column(w) : w;
+    }
+  out->nr = (uint32_t)nr;
+  uint8_t blk[64];
+  for (int pass = 0; pass < 2; pass++) {
+    const uint8_t pad = pass ? 0x5c : 0x36;
+    for (size_t i = 0; i < 64; i++) blk[i] = (uint8_t)((i < mac_len ? key[i] : 0) ^ pad);
+    uint32_t *h = pass ? out->outer : out->inner;
+    if (mac_len == 20) {
+      static const uint32_t kSha1Init[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u,
+                                            0xc3d2e1f0u};
+      for (int i = 0; i < 5; i++) h[i] = kSha1Init[i];
+      sha1_block(h, blk);
+    } else {
+      for (int i = 0; i < 8; i++) h[i] = kSha256Init[i];
+      sha256_block(h, blk);
+    }
+  }
+  secure_zero(blk, sizeof(blk));
+  secure_zero(rk, sizeof(rk));
+  return true;
+}
+
+namespace {
+
 // Key i's tables from raw key bytes keys[i * key_len ...].  The tables are
 // written by their own lane (12,816 B each, scattered 16-byte stores that
 // L2 merges into full lines).

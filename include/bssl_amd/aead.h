@@ -111,6 +111,50 @@ BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_eax(void);             /* aead.
  * reject them with CIPHER_R_CTRL_NOT_IMPLEMENTED. */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_ctr_hmac_sha256(void); /* aead.h:135 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_ctr_hmac_sha256(void); /* aead.h:139 */
+/* The TLS 1.1 / 1.2 MAC-then-encrypt AEADs with an explicit IV (e_tls.cc,
+ * tls_cbc.cc): AES-CBC over plaintext || HMAC || padding.  The key is the MAC
+ * key (20 bytes HMAC-SHA1, 32 bytes HMAC-SHA256) followed by the AES key: 36,
+ * 52 and 48 bytes; the nonce is the 16-byte CBC IV; the AD is the 13-byte TLS
+ * header without its length, 11 bytes; the overhead is 36, 36 and 48.
+ *   mac  = HMAC(ad || be16(in_len mod 2^16) || in)   (a record of 65536 bytes
+ *          or more wraps silently, as in the reference)
+ *   wire = AES-CBC(iv = nonce, in || mac || pad_len x byte(pad_len - 1)),
+ *          pad_len = 16 - (in_len + mac_len) mod 16
+ * The first in_len bytes of `wire` are the ciphertext, the other mac_len +
+ * pad_len the tag; EVP_AEAD_CTX_tag_len computes that length from in_len +
+ * extra_in_len, and the context's own tag_len stays 0.  Rules as in the
+ * reference:
+ *  - EVP_AEAD_CTX_init and EVP_AEAD_CTX_new fail with
+ *    CIPHER_R_NO_DIRECTION_SET; EVP_AEAD_CTX_init_with_direction is the way
+ *    in, and the context then seals or opens, never both: the other direction
+ *    is CIPHER_R_INVALID_OPERATION.  Another key length is
+ *    CIPHER_R_UNSUPPORTED_KEY_SIZE, a tag_len other than 0 or the MAC size
+ *    CIPHER_R_UNSUPPORTED_TAG_SIZE.
+ *  - seal: a tag buffer below the record's tag length is
+ *    CIPHER_R_BUFFER_TOO_SMALL, then a nonce other than 16 bytes
+ *    CIPHER_R_INVALID_NONCE_SIZE, then an AD other than 11 bytes
+ *    CIPHER_R_INVALID_AD_SIZE.
+ *  - open takes the whole wire fragment: max_out_len below in_len is
+ *    CIPHER_R_BUFFER_TOO_SMALL, in_len below the MAC size CIPHER_R_BAD_DECRYPT
+ *    (before the nonce and AD checks), a length that is no multiple of 16 or
+ *    below mac_len + 1, a wrong padding and a wrong MAC all
+ *    CIPHER_R_BAD_DECRYPT.  Padding of up to 256 bytes is accepted.  On success
+ *    out[0, in_len) holds the whole decryption (plaintext, MAC, padding) and
+ *    *out_len the plaintext length; on failure `out` is zeroed.  The open
+ *    kernel's work does not depend on the padding or on where it failed
+ *    (DESIGN.md 4.14).
+ *  - EVP_AEAD_CTX_open_gather and _openv_detached return 0 with
+ *    CIPHER_R_CTRL_NOT_IMPLEMENTED (aead.cc.inc:567-575); _seal_scatter (with
+ *    extra_in), _sealv and _openv work.
+ * They work with the contiguous device batches and keysets below (see
+ * BSSL_AMD_BATCH and BSSL_AMD_KEYSET_new_with_direction).  Not supported: the
+ * _implicit_iv variants (aead.h:566, 569: TLS 1.0 chains the IV from record to
+ * record), the 3DES AEADs (aead.h:570-571), and, for these AEADs, the iovec
+ * device batches and the TLS record layer (tls.h), which reject them with
+ * CIPHER_R_CTRL_NOT_IMPLEMENTED and launch nothing. */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_cbc_sha1_tls(void);   /* aead.h:565 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_cbc_sha1_tls(void);   /* aead.h:567 */
+BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_cbc_sha256_tls(void); /* aead.h:568 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls12(void);  /* aead.h:583 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_256_gcm_tls12(void);  /* aead.h:584 */
 BSSL_AMD_EXPORT const EVP_AEAD *EVP_aead_aes_128_gcm_tls13(void);  /* aead.h:585 */
@@ -203,6 +247,7 @@ BSSL_AMD_EXPORT void ERR_clear_error(void);
 #define CIPHER_R_BAD_KEY_LENGTH 102
 #define CIPHER_R_BUFFER_TOO_SMALL 103
 #define CIPHER_R_CTRL_NOT_IMPLEMENTED 104
+#define CIPHER_R_INVALID_AD_SIZE 109     /* cipher.h:801 */
 #define CIPHER_R_INVALID_NONCE_SIZE 111
 #define CIPHER_R_INVALID_OPERATION 112  /* cipher.h:804 */
 #define CIPHER_R_NO_DIRECTION_SET 124
@@ -249,6 +294,20 @@ typedef struct bssl_amd_batch_st {
   /* Keysets only: key_index[i] selects the key of record i.  Records with
    * equal key_index should be contiguous for speed (any order is correct). */
   const uint32_t *key_index;
+  /* The TLS AES-CBC-HMAC AEADs only (ignored by every other AEAD; may be
+   * NULL).  For them: seal writes record i's tag to the slot tags +
+   * i*EVP_AEAD_max_overhead(aead) (36 or 48 bytes: the first mac_len + pad_len
+   * bytes are the tag, the rest is written as zero; body || tag is the wire
+   * fragment); a failed record has a zeroed body and slot.  Open reads the
+   * whole wire fragment, lengths[i] bytes at in + offset_i (`tags` is unused
+   * and may be NULL), writes the whole decryption to the same offset of `out`
+   * and the plaintext length to out_lengths[i]; a failed record (bad padding or
+   * MAC, a length that is no multiple of 16 or below mac_len + 1) gets zeros
+   * and out_lengths[i] = 0.  The batch is not launched when nonce_len != 16
+   * (CIPHER_R_INVALID_NONCE_SIZE) or when ad_lengths == NULL and ad_len != 11
+   * (CIPHER_R_INVALID_AD_SIZE); with ad_lengths, a record whose AD is not 11
+   * bytes fails alone. */
+  uint64_t *out_lengths;
 } BSSL_AMD_BATCH;
 
 /* Seal / open every record of `batch` with the key of `ctx` (key_index is
@@ -286,7 +345,7 @@ BSSL_AMD_EXPORT int EVP_AEAD_CTX_open_batch_device(const EVP_AEAD_CTX *ctx,
  * `hip_stream` (one small kernel for the per-record totals, then the bulk
  * kernels) and never synchronises it.  Chunks of one batch must not partially
  * overlap (aead.cc.inc:281-308; not checked on the device).
- * Not implemented for the AES-CCM, AES-EAX and AES-CTR-HMAC contexts: both calls return 0
+ * Not implemented for the AES-CCM, AES-EAX, AES-CTR-HMAC and TLS AES-CBC-HMAC contexts: both calls return 0
  * with CIPHER_R_CTRL_NOT_IMPLEMENTED and launch nothing (their host sealv /
  * openv calls gather the chunks and work). */
 typedef struct bssl_amd_iov_batch_st {
@@ -315,6 +374,13 @@ BSSL_AMD_EXPORT BSSL_AMD_KEYSET *BSSL_AMD_KEYSET_new(const EVP_AEAD *aead,
                                                      const uint8_t *keys,
                                                      size_t num_keys,
                                                      size_t tag_len);
+/* Keys that work in one direction (the TLS AES-CBC-HMAC AEADs, which
+ * BSSL_AMD_KEYSET_new rejects with CIPHER_R_NO_DIRECTION_SET): a keyset used
+ * against its direction fails with CIPHER_R_INVALID_OPERATION.  For every
+ * other AEAD `dir` is ignored. */
+BSSL_AMD_EXPORT BSSL_AMD_KEYSET *BSSL_AMD_KEYSET_new_with_direction(
+    const EVP_AEAD *aead, const uint8_t *keys, size_t num_keys, size_t tag_len,
+    enum evp_aead_direction_t dir);
 BSSL_AMD_EXPORT void BSSL_AMD_KEYSET_free(BSSL_AMD_KEYSET *ks);
 BSSL_AMD_EXPORT size_t BSSL_AMD_KEYSET_num_keys(const BSSL_AMD_KEYSET *ks);
 BSSL_AMD_EXPORT int BSSL_AMD_KEYSET_seal_batch_device(

@@ -41,7 +41,9 @@ typedef struct bssl_amd_tls_aead_st BSSL_AMD_TLS_AEAD;
  * start at 0, which the tls13 AEAD's nonce check relies on, e_aes.cc.inc:
  * 1181-1185).  Returns NULL on error; any other AEAD (AES-GCM-SIV, XChaCha,
  * AES-CCM, AES-EAX: the reference's TLS stack has no such suites) is rejected
- * with CIPHER_R_UNSUPPORTED_KEY_SIZE, the AES-CTR-HMAC-SHA256 AEADs with
+ * with CIPHER_R_UNSUPPORTED_KEY_SIZE, the AES-CTR-HMAC-SHA256 AEADs and the
+ * TLS AES-CBC-HMAC AEADs (EVP_aead_aes_*_cbc_sha*_tls: the CBC suites' record
+ * layer, with its random explicit IVs and MAC key, is not built here) with
  * CIPHER_R_CTRL_NOT_IMPLEMENTED. */
 BSSL_AMD_EXPORT BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(
     enum evp_aead_direction_t direction, uint16_t version, const EVP_AEAD *aead,

@@ -86,7 +86,9 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_TLS_AEAD_new", "BSSL_AMD_TLS_AEAD_free", "BSSL_AMD_TLS_AEAD_prefix_len",
     "BSSL_AMD_TLS_AEAD_suffix_len", "BSSL_AMD_TLS_AEAD_sequence",
     "BSSL_AMD_TLS_AEAD_seal_records_device", "BSSL_AMD_TLS_AEAD_open_records_device",
+    "BSSL_AMD_TLS_AEAD_new_cbc", "BSSL_AMD_test_tls_set_iv_key",
 ]
+TLS1_1_VERSION = 0x0302
 TLS1_2_VERSION = 0x0303
 TLS1_3_VERSION = 0x0304
 
@@ -126,6 +128,8 @@ class BSSL_AMD_TLS_RECORDS(ctypes.Structure):
         ("num_records", _S), ("in_", _P), ("out", _P), ("offsets", _P), ("lengths", _P),
         ("record_stride", ctypes.c_uint64), ("record_len", ctypes.c_uint64), ("types", _P),
         ("type", ctypes.c_uint8), ("prefix", _P), ("suffix", _P), ("status", _P),
+        # read for CBC contexts only (TlsAead.new_cbc)
+        ("out_lengths", _P), ("explicit_ivs", _P),
     ]
 
 
@@ -179,6 +183,8 @@ _SIGS = {
     "BSSL_AMD_test_set_bs_ek0_producers": (_I, [_I]),
     "BSSL_AMD_test_set_gcm_mix": (_I, [_I]),
     "BSSL_AMD_TLS_AEAD_new": (_P, [_I, ctypes.c_uint16, _P, _P, _S, _P, _S, ctypes.c_uint64]),
+    "BSSL_AMD_TLS_AEAD_new_cbc": (_P, [_I, ctypes.c_uint16, _P, _P, _S, _P, _S, ctypes.c_uint64]),
+    "BSSL_AMD_test_tls_set_iv_key": (_I, [_P, _P]),
     "BSSL_AMD_TLS_AEAD_free": (None, [_P]),
     "BSSL_AMD_TLS_AEAD_prefix_len": (_S, [_P]),
     "BSSL_AMD_TLS_AEAD_suffix_len": (_S, [_P]),
@@ -401,6 +407,20 @@ class TlsAead:
         if not self.h:
             _fail("BSSL_AMD_TLS_AEAD_new")
 
+    @classmethod
+    def new_cbc(cls, direction, version, aead, enc_key, mac_key, seq=0):
+        """BSSL_AMD_TLS_AEAD_new_cbc: a TLS 1.1 / 1.2 AES-CBC-HMAC suite with
+        the split keys of SSLAEADContext::Create."""
+        if isinstance(aead, str):
+            aead = EVP_aead(aead)
+        enc_key, mac_key = bytes(enc_key), bytes(mac_key)
+        self = cls.__new__(cls)
+        self.h = _lib.BSSL_AMD_TLS_AEAD_new_cbc(direction, version, aead, enc_key, len(enc_key),
+                                                mac_key, len(mac_key), seq)
+        if not self.h:
+            _fail("BSSL_AMD_TLS_AEAD_new_cbc")
+        return self
+
     @property
     def prefix_len(self):
         return _lib.BSSL_AMD_TLS_AEAD_prefix_len(self.h)
@@ -436,8 +456,11 @@ class TlsAead:
 
 
 def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, lengths=None,
-                     record_stride=0, record_len=0, types=None, type_=23, status=None):
-    """BSSL_AMD_TLS_RECORDS from torch device tensors (keeps references)."""
+                     record_stride=0, record_len=0, types=None, type_=23, status=None,
+                     out_lengths=None, explicit_ivs=None):
+    """BSSL_AMD_TLS_RECORDS from torch device tensors (keeps references).
+    suffix may be None for a CBC open; out_lengths / explicit_ivs are read for
+    CBC contexts only."""
     r = BSSL_AMD_TLS_RECORDS()
     r.num_records = num_records
     r.in_, r.out = _dptr(inp), _dptr(out)
@@ -445,7 +468,8 @@ def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, len
     r.record_stride, r.record_len = record_stride, record_len
     r.types, r.type = _dptr(types), type_
     r.prefix, r.suffix, r.status = _dptr(prefix), _dptr(suffix), _dptr(status)
-    r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status)
+    r.out_lengths, r.explicit_ivs = _dptr(out_lengths), _dptr(explicit_ivs)
+    r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status, out_lengths, explicit_ivs)
     return r
 
 

@@ -8,8 +8,10 @@
 // (gcm.hip, chacha.hip): single-record calls upload their host buffers, run a
 // one-record batch and download the result.
 #include <hip/hip_runtime.h>
+#include <errno.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/random.h>
 
 #include <new>
 #include <vector>
@@ -1714,6 +1716,11 @@ struct bssl_amd_tls_aead_st {
   uint32_t explicit_len;
   uint8_t fixed_iv[12];
   uint64_t seq;
+  // The CBC suites (BSSL_AMD_TLS_AEAD_new_cbc): the record version, and for a
+  // sealing context the key of the IV generator (tls_records.hip).
+  bool cbc;
+  uint16_t version;
+  uint8_t iv_key[32];
 };
 
 namespace {
@@ -1727,7 +1734,95 @@ const EVP_AEAD *tls_record_aead(const EVP_AEAD *aead, bool tls13) {
   return nullptr;
 }
 
+// The CBC suites: random_variable_nonce_ / omit_length_in_ad_ of
+// SSLAEADContext (ssl_aead_ctx.cc:109-113) and the limits of tls_open_record
+// (tls_record.cc:117-133, 204-209).
+int tls_cbc_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *stream) {
+  // Open takes whole fragments (no suffix) and must report the lengths.
+  if (!r || (r->num_records && (!r->in || !r->out || !r->prefix ||
+                                (t->seal ? !r->suffix : !r->out_lengths)))) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return 0;
+  }
+  const uint64_t n = r->num_records;
+  if (n == 0) return 1;
+  if (t->seq > UINT64_MAX - n) {
+    PUT_ERROR(ERR_R_OVERFLOW);
+    return 0;
+  }
+  const EVP_AEAD_CTX *ctx = &t->ctx;
+  CtxState *st = state_of(ctx);
+  if (!on_key_device(st->km)) return 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t mac_len = (uint32_t)tls_cbc_mac_len(ctx->aead);
+  // Scratch: IVs (16 B), AD (11 B) and flags per record.
+  uint8_t *buf = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void **>(&buf), n * (16 + 11 + 1), s) != hipSuccess) {
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return 0;
+  }
+  uint8_t *d_iv = buf, *d_ad = d_iv + 16 * n, *d_valid = d_ad + 11 * n;
+  int ok = hipMemsetAsync(d_valid, 1, n, s) == hipSuccess;
+  TlsCbcPrepare p;
+  memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.lengths = r->lengths;
+  p.record_len = r->record_len;
+  p.types = t->seal ? r->types : nullptr;
+  p.type = r->type;
+  p.record_version = t->version;
+  p.mac_len = mac_len;
+  p.seq = t->seq;
+  p.open = !t->seal;
+  p.explicit_ivs = t->seal ? r->explicit_ivs : nullptr;
+  if (t->seal) memcpy(p.iv_key, t->iv_key, sizeof(p.iv_key));  // (little-endian host)
+  p.nonces = d_iv;
+  p.prefix = r->prefix;
+  p.ad = d_ad;
+  p.valid = d_valid;
+  p.types_out = t->seal ? nullptr : r->types;
+  if (ok) ok = launch_tls_cbc_prepare(p, stream) == 0;
+  secure_zero(&p, sizeof(p));
+  if (ok) {
+    BatchDesc d;
+    memset(&d, 0, sizeof(d));
+    d.in = r->in;
+    d.out = r->out;
+    d.offsets = r->offsets;
+    d.lengths = r->lengths;
+    d.record_stride = r->record_stride;
+    d.record_len = r->record_len;
+    d.nonces = d_iv;
+    d.nonce_len = 16;
+    d.ad = d_ad;
+    d.ad_stride = 11;
+    d.ad_len = 11;
+    d.tags = r->suffix;
+    d.status = r->status;
+    d.num_records = n;
+    d.tag_len = ctx->aead->overhead;  // the slot: the MAC and the longest padding
+    d.num_keys = 1;
+    d.valid = d_valid;
+    if (!t->seal) {
+      d.out_lengths = r->out_lengths;
+      d.max_plain_len = kTlsMaxPlainLen;
+    }
+    const KernelEvents *ev = timing_pair();
+    ok = launch_tls_cbc(static_cast<const TlsCbcKeyDev *>(st->km->dev), d, mac_len == 20, !t->seal,
+                        st->km->nr, stream, ev) == 0;
+    t_timing.last_name = "tls_cbc_kernel";
+  }
+  hipFreeAsync(buf, s);
+  if (!ok) {
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return 0;
+  }
+  t->seq += n;
+  return 1;
+}
+
 int tls_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *stream) {
+  if (t && t->cbc) return tls_cbc_records(t, r, stream);
   if (!t || !r || (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix))) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return 0;
@@ -1895,6 +1990,9 @@ BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(enum evp_aead_direction_t direction, ui
   memset(t->fixed_iv, 0, sizeof(t->fixed_iv));
   memcpy(t->fixed_iv, fixed_iv, fixed_iv_len);
   t->seq = seq;
+  t->cbc = false;
+  t->version = 0x0303;
+  memset(t->iv_key, 0, sizeof(t->iv_key));
   if (t->seal && tls13 && t->ctx.aead->tls == 13 && seq != 0) {
     // The tls13 AEAD takes its nonce mask from the first sealed nonce, which
     // it assumes is sequence number 0 (e_aes.cc.inc:1181-1185).  A writer
@@ -1907,15 +2005,88 @@ BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(enum evp_aead_direction_t direction, ui
   return t;
 }
 
+BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new_cbc(enum evp_aead_direction_t direction, uint16_t version,
+                                             const EVP_AEAD *aead, const uint8_t *enc_key,
+                                             size_t enc_key_len, const uint8_t *mac_key,
+                                             size_t mac_key_len, uint64_t seq) {
+  // SSLAEADContext::Create (ssl_aead_ctx.cc:95-114) for a CBC suite with an
+  // explicit IV: TLS 1.1 and 1.2, no fixed IV.
+  if ((version != BSSL_AMD_TLS1_1_VERSION && version != BSSL_AMD_TLS1_2_VERSION) || !aead ||
+      !enc_key || !mac_key) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return nullptr;
+  }
+  if (aead->kind != kAeadTlsCbc) {
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
+    return nullptr;
+  }
+  if (mac_key_len != tls_cbc_mac_len(aead) || mac_key_len + enc_key_len != aead->key_len) {
+    PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
+    return nullptr;
+  }
+  BSSL_AMD_TLS_AEAD *t = new (std::nothrow) bssl_amd_tls_aead_st;
+  if (!t) {
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return nullptr;
+  }
+  memset(t->iv_key, 0, sizeof(t->iv_key));
+  t->seal = direction == evp_aead_seal;
+  if (t->seal) {
+    // The IV generator's key (RAND_bytes per record in the reference,
+    // ssl_aead_ctx.cc:343-347).
+    size_t got = 0;
+    while (got < sizeof(t->iv_key)) {
+      const ssize_t k = getrandom(t->iv_key + got, sizeof(t->iv_key) - got, 0);
+      if (k < 0 && errno == EINTR) continue;
+      if (k <= 0) break;
+      got += (size_t)k;
+    }
+    if (got != sizeof(t->iv_key)) {
+      secure_zero(t->iv_key, sizeof(t->iv_key));
+      delete t;
+      PUT_ERROR(ERR_R_INTERNAL_ERROR);
+      return nullptr;
+    }
+  }
+  uint8_t merged[64];  // MAC key || AES key, at most 52 bytes
+  memcpy(merged, mac_key, mac_key_len);
+  memcpy(merged + mac_key_len, enc_key, enc_key_len);
+  EVP_AEAD_CTX_zero(&t->ctx);
+  const int ok = EVP_AEAD_CTX_init_with_direction(&t->ctx, aead, merged, mac_key_len + enc_key_len,
+                                                  EVP_AEAD_DEFAULT_TAG_LENGTH, direction);
+  secure_zero(merged, sizeof(merged));
+  if (!ok) {
+    secure_zero(t->iv_key, sizeof(t->iv_key));
+    delete t;
+    return nullptr;
+  }
+  t->tls13 = false;
+  t->xor_nonce = false;
+  t->explicit_len = 16;
+  memset(t->fixed_iv, 0, sizeof(t->fixed_iv));
+  t->seq = seq;
+  t->cbc = true;
+  t->version = version;
+  return t;
+}
+
 void BSSL_AMD_TLS_AEAD_free(BSSL_AMD_TLS_AEAD *t) {
   if (!t) return;
   EVP_AEAD_CTX_cleanup(&t->ctx);
+  secure_zero(t->iv_key, sizeof(t->iv_key));
   delete t;
+}
+
+int BSSL_AMD_test_tls_set_iv_key(BSSL_AMD_TLS_AEAD *t, const uint8_t key[32]) {
+  if (!t || !t->cbc || !t->seal || !key) return 0;
+  memcpy(t->iv_key, key, sizeof(t->iv_key));
+  return 1;
 }
 
 size_t BSSL_AMD_TLS_AEAD_prefix_len(const BSSL_AMD_TLS_AEAD *t) { return 5 + t->explicit_len; }
 
 size_t BSSL_AMD_TLS_AEAD_suffix_len(const BSSL_AMD_TLS_AEAD *t) {
+  if (t->cbc) return t->ctx.aead->overhead;  // the tag slot: the MAC and the longest padding
   return (t->tls13 ? 1 : 0) + t->ctx.tag_len;
 }
 

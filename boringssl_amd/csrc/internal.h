@@ -205,6 +205,10 @@ struct BatchDesc {
   // TLS AES-CBC-HMAC open only (BSSL_AMD_BATCH::out_lengths): record i's
   // plaintext length goes here (0 for a failed record).  Null: not reported.
   uint64_t *out_lengths;
+  // TLS AES-CBC-HMAC open only: a record whose plaintext is longer fails like
+  // one with a bad MAC (tls_record.cc:204-209, SSL3_RT_MAX_PLAIN_LENGTH).  Set
+  // by the TLS record layer only; 0: no limit.
+  uint64_t max_plain_len;
 };
 
 // Tag / extra addresses of record i.
@@ -339,6 +343,31 @@ struct TlsPrepare {
   uint8_t *nonces, *prefix, *ad, *extra, *valid;
 };
 int launch_tls_prepare(const TlsPrepare &p, void *stream);
+// ... and of the TLS 1.1 / 1.2 AES-CBC-HMAC suites: the 16-byte CBC IV (seal:
+// the caller's, or bytes 0..15 of the ChaCha20 block of iv_key with counter
+// (uint32)seq and nonce words (uint32)(seq >> 32), 0, 0; open: the received
+// one, prefix + 5), the 11-byte AD be64(seq) || type || version, on seal the
+// 21-byte prefix (header with the padded length, then the IV), on open the
+// header type; and valid[i] = 0 for the publicly invalid records.
+struct TlsCbcPrepare {
+  uint64_t n;
+  const uint64_t *lengths;  // or record_len for all
+  uint64_t record_len;
+  const uint8_t *types;     // seal: or `type` for all
+  uint8_t type;
+  uint16_t record_version;  // 0x0302 or 0x0303: header and AD
+  uint32_t mac_len;         // 20 or 32
+  uint64_t seq;
+  int open;
+  const uint8_t *explicit_ivs;  // seal: 16 bytes per record, or null: generated
+  uint32_t iv_key[8];           // the generator's key, little-endian words
+  uint8_t *nonces, *prefix, *ad, *valid;
+  uint8_t *types_out;           // open: receives the header types, or null
+};
+int launch_tls_cbc_prepare(const TlsCbcPrepare &p, void *stream);
+// Record-layer limits (include/openssl/ssl3.h of the reference).
+constexpr uint64_t kTlsMaxPlainLen = 16384;
+constexpr uint64_t kTlsMaxEncryptedLen = 16384 + 320;
 // Batches of non-contiguous records (iovec.hip).
 struct IovBatchDesc {
   uint64_t num_records;

@@ -152,8 +152,8 @@ __device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {
 // batch layout -- with the table lookups' bank argument of aes_inv_tables.h.
 // The padding byte p, data_len and the two verdicts enter selects, masks and
 // shift amounts of VALU instructions only.  Names below: `len`, `nblk`, `kh`,
-// `kmin`, `jtrail` and `dist*` are public; `p`, `padlen`, `dlen`, `bad`,
-// `macacc`, `dig` are not.
+// `kmin`, `jtrail`, `dist*` and `cap` (the record layer's plaintext limit) are
+// public; `p`, `padlen`, `dlen`, `bad`, `macacc`, `dig`, `over` are not.
 template <bool OPEN, int NR, bool SHA1, bool KEYSET>
 __global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_kernel(
     const TlsCbcKeyDev *__restrict__ keys, BatchDesc b) {
@@ -417,7 +417,11 @@ __global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_k
       uint32_t diff = 0;
 #pragma unroll
       for (int i = 0; i < H::kWords; i++) diff |= __builtin_bswap32(h[i]) ^ macacc[i];
-      ok = (diff | bad | ~fits) == 0;
+      // The record layer's plaintext limit (tls_record.cc:204-209): all ones
+      // where dlen exceeds it, one more term of the verdict.
+      const uint64_t cap = b.max_plain_len ? b.max_plain_len : ~uint64_t(0) >> 1;
+      const uint32_t over = (uint32_t)((int64_t)(cap - dlen) >> 63);
+      ok = (diff | bad | ~fits | over) == 0;
     }
   }
   if (!active) return;

@@ -8,6 +8,7 @@
 #define BSSL_AMD_TEST_HOOKS_H
 
 #include "bssl_amd/aead.h"
+#include "bssl_amd/tls.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -38,6 +39,11 @@ BSSL_AMD_EXPORT int BSSL_AMD_test_set_bs_ek0_producers(int on);
  * the previous engine (restore it with BSSL_AMD_set_aes_gcm_engine), -1 for
  * another wave count. */
 BSSL_AMD_EXPORT int BSSL_AMD_test_set_gcm_mix(int bitsliced_waves);
+
+/* Replaces the key of a sealing CBC record-layer context's IV generator
+ * (BSSL_AMD_TLS_AEAD_new_cbc), so a test can predict the explicit IVs.
+ * Returns 1 for a sealing CBC context, 0 (nothing changed) otherwise. */
+BSSL_AMD_EXPORT int BSSL_AMD_test_tls_set_iv_key(BSSL_AMD_TLS_AEAD *t, const uint8_t key[32]);
 
 #ifdef __cplusplus
 }

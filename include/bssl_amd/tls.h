@@ -17,6 +17,25 @@
  * so header ++ prefix-rest ++ body ++ suffix is the wire record.  TLS 1.3
  * records are sealed without padding; open expects unpadded records (the
  * inner type is the byte after the body) and returns it in types[i].
+ *
+ * The TLS 1.1 / 1.2 AES-CBC-HMAC suites (BSSL_AMD_TLS_AEAD_new_cbc; the
+ * reference's SSLAEADContext with a MAC key, ssl_aead_ctx.cc:95-114) have
+ * another layout.  With mac_len 20 (SHA-1) or 32 (SHA-256) and, for a
+ * plaintext of len bytes, pad_len = 16 - (len + mac_len) mod 16:
+ *   prefix[i]  21 bytes: type, be16(version), be16(16 + len + mac_len +
+ *              pad_len), then the 16-byte explicit IV
+ *   body       seal: the first len bytes of the CBC output.  Open: the whole
+ *              fragment after the IV (body, MAC and padding together, a
+ *              multiple of 16 bytes) at in + offsets[i], lengths[i] bytes; the
+ *              whole decryption goes to out + offsets[i] and the plaintext
+ *              length to out_lengths[i]
+ *   suffix[i]  seal: suffix_len bytes (the AEAD's overhead, 36 or 48), of
+ *              which the first mac_len + pad_len hold the rest of the CBC
+ *              output and the others are zero; prefix ++ body ++
+ *              suffix[0, mac_len + pad_len) is the wire record.  Open: unused,
+ *              may be NULL
+ * and the additional data is be64(seq) ++ type ++ be16(version), 11 bytes
+ * (open: the type of the received header).
  */
 #ifndef BSSL_AMD_TLS_H
 #define BSSL_AMD_TLS_H
@@ -27,6 +46,7 @@
 extern "C" {
 #endif
 
+#define BSSL_AMD_TLS1_1_VERSION 0x0302
 #define BSSL_AMD_TLS1_2_VERSION 0x0303
 #define BSSL_AMD_TLS1_3_VERSION 0x0304
 
@@ -42,12 +62,35 @@ typedef struct bssl_amd_tls_aead_st BSSL_AMD_TLS_AEAD;
  * 1181-1185).  Returns NULL on error; any other AEAD (AES-GCM-SIV, XChaCha,
  * AES-CCM, AES-EAX: the reference's TLS stack has no such suites) is rejected
  * with CIPHER_R_UNSUPPORTED_KEY_SIZE, the AES-CTR-HMAC-SHA256 AEADs and the
- * TLS AES-CBC-HMAC AEADs (EVP_aead_aes_*_cbc_sha*_tls: the CBC suites' record
- * layer, with its random explicit IVs and MAC key, is not built here) with
+ * TLS AES-CBC-HMAC AEADs (EVP_aead_aes_*_cbc_sha*_tls: the CBC suites have
+ * split keys and no fixed IV, see BSSL_AMD_TLS_AEAD_new_cbc) with
  * CIPHER_R_CTRL_NOT_IMPLEMENTED. */
 BSSL_AMD_EXPORT BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(
     enum evp_aead_direction_t direction, uint16_t version, const EVP_AEAD *aead,
     const uint8_t *key, size_t key_len, const uint8_t *fixed_iv, size_t fixed_iv_len,
+    uint64_t seq);
+/* SSLAEADContext::Create for a CBC cipher suite of TLS 1.1 or 1.2 (explicit
+ * IV; ssl_aead_ctx.cc:95-114): `aead` is EVP_aead_aes_128_cbc_sha1_tls(),
+ * EVP_aead_aes_256_cbc_sha1_tls() or EVP_aead_aes_128_cbc_sha256_tls(), the
+ * context EVP_AEAD_CTX_init_with_direction(aead, mac_key ++ enc_key, tag
+ * length 0, direction).  `version` (0x0302 or 0x0303) is also the record
+ * version of the header and of the additional data.  There is no fixed IV:
+ * that is the TLS 1.0 implicit-IV form, which is not supported.  Checked before
+ * any GPU call: another version, a NULL aead or key is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; another AEAD CIPHER_R_CTRL_NOT_IMPLEMENTED;
+ * mac_key_len other than the MAC size (20 or 32), or mac_key_len + enc_key_len
+ * other than EVP_AEAD_key_length(aead), CIPHER_R_UNSUPPORTED_KEY_SIZE.
+ * prefix_len is 21, suffix_len EVP_AEAD_max_overhead(aead) (36 or 48).
+ *
+ * A sealing context draws a 32-byte key from getrandom(2) (failure:
+ * ERR_R_INTERNAL_ERROR) for the explicit IVs it generates: the IV of sequence
+ * number s is bytes 0..15 of the ChaCha20 block (RFC 8439 2.3) of that key
+ * with block counter (uint32)s and nonce words (uint32)(s >> 32), 0, 0 --
+ * unpredictable without the key, one block per sequence number.  The key
+ * stays in the host object and is zeroed by BSSL_AMD_TLS_AEAD_free. */
+BSSL_AMD_EXPORT BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new_cbc(
+    enum evp_aead_direction_t direction, uint16_t version, const EVP_AEAD *aead,
+    const uint8_t *enc_key, size_t enc_key_len, const uint8_t *mac_key, size_t mac_key_len,
     uint64_t seq);
 BSSL_AMD_EXPORT void BSSL_AMD_TLS_AEAD_free(BSSL_AMD_TLS_AEAD *t);
 BSSL_AMD_EXPORT size_t BSSL_AMD_TLS_AEAD_prefix_len(const BSSL_AMD_TLS_AEAD *t);
@@ -70,6 +113,15 @@ typedef struct {
   uint8_t *prefix; /* device, prefix_len bytes per record */
   uint8_t *suffix; /* device, suffix_len bytes per record */
   uint8_t *status; /* device, 1 byte per record (1 = sealed / authentic), or NULL */
+  /* The two fields below are read for CBC contexts (BSSL_AMD_TLS_AEAD_new_cbc)
+   * only: a caller of the AEAD suites compiled against the structure without
+   * them keeps working. */
+  /* CBC open: receives record i's plaintext length, 0 for a failed record
+   * (device).  Required for CBC open. */
+  uint64_t *out_lengths;
+  /* CBC seal: the explicit IVs to use, 16 bytes per record (device), or NULL:
+   * generated (BSSL_AMD_TLS_AEAD_new_cbc).  Ignored on open. */
+  const uint8_t *explicit_ivs;
 } BSSL_AMD_TLS_RECORDS;
 
 /* Seal (open) num_records records with sequence numbers sequence() ..
@@ -78,7 +130,18 @@ typedef struct {
  * zeroed outputs; it still consumes its sequence number.  Returns 0 (nothing
  * launched, error queued) when the sequence number would wrap
  * (tls_record.cc:305-308) or on argument errors.  Synchronises the stream
- * for AES-GCM seal (the nonce state, see EVP_AEAD_CTX_seal_batch_device). */
+ * for AES-GCM seal (the nonce state, see EVP_AEAD_CTX_seal_batch_device); a
+ * CBC seal, with generated IVs too, only enqueues work.
+ *
+ * CBC open (tls_open_record + SSLAEADContext::Open): prefix[i] holds the
+ * received header and IV; the header type goes to types[i] when `types` is
+ * given.  A record fails alone (status 0, lengths[i] zero bytes of output,
+ * out_lengths[i] 0) when the header's version is not the context's
+ * (tls_record.cc:117-130), its length is not 16 + lengths[i], 16 + lengths[i]
+ * exceeds 16704 (SSL3_RT_MAX_ENCRYPTED_LENGTH, :133), lengths[i] is no
+ * multiple of 16 or below mac_len + 1, the padding or the MAC is wrong, or the
+ * plaintext is longer than 2^14 bytes (:204-209).  out_lengths == NULL is an
+ * argument error (ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED, nothing launched). */
 BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_seal_records_device(BSSL_AMD_TLS_AEAD *t,
                                                           const BSSL_AMD_TLS_RECORDS *r,
                                                           void *hip_stream);

@@ -14,6 +14,7 @@
 #include <sys/random.h>
 
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "bssl_amd/aead.h"
@@ -110,8 +111,8 @@ struct KeyMaterial {
   int device;  // the HIP device the key material lives on
   size_t num_keys;
   int nr;
-  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], CtrHmacKeyDev[num_keys],
-  // TlsCbcKeyDev[num_keys] or ChaChaKeyDev[num_keys]
+  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], AesHmacKeyDev[num_keys] or
+  // ChaChaKeyDev[num_keys]
   void *dev;
   size_t bytes;
   // kAeadTlsCbc: the one direction the keys work in (e_tls.cc:125-129, 274-278).
@@ -180,6 +181,20 @@ bool tls_cbc_direction_ok(const KeyMaterial *km, bool open) {
   return false;
 }
 
+// km's keys (km->num_keys of km->aead->key_len bytes each) through a per-key
+// setup function into `host`, which the caller wipes; km->nr from key 0 where
+// the key material has one.  false: a key was rejected.
+template <class KeyDev, class Setup>
+bool setup_host_keys(KeyMaterial *km, const uint8_t *keys, std::vector<uint8_t> &host,
+                     Setup setup) {
+  host.resize(km->num_keys * sizeof(KeyDev));
+  KeyDev *h = reinterpret_cast<KeyDev *>(host.data());
+  for (size_t i = 0; i < km->num_keys; i++)
+    if (!setup(keys + i * km->aead->key_len, &h[i])) return false;
+  if constexpr (!std::is_same_v<KeyDev, ChaChaKeyDev>) km->nr = (int)h[0].nr;
+  return true;
+}
+
 // Key material of num_keys keys on the current device.  AES-GCM(-SIV) key
 // sets of kDeviceKeySetupMin keys or more are expanded by the device kernel
 // straight into device memory (gcm_key_setup_device); smaller ones -- the
@@ -214,63 +229,40 @@ KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_key
     km->nr = (int)aead->key_len / 4 + 6;
     return km;
   }
-  size_t bytes;
   std::vector<uint8_t> host;
   struct Wipe {  // the expanded keys in host memory are wiped on every path
     std::vector<uint8_t> &v;
     ~Wipe() { secure_zero(v.data(), v.size()); }
   } wipe{host};
-  if (aead->kind == kAeadAesGcm || aead->kind == kAeadAesGcmSiv) {
-    bytes = num_keys * sizeof(GcmKeyDev);
-    host.resize(bytes);
-    GcmKeyDev *h = reinterpret_cast<GcmKeyDev *>(host.data());
-    for (size_t i = 0; i < num_keys; i++) {
-      if (!gcm_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
-        delete km;
-        return nullptr;
-      }
-    }
-    km->nr = (int)h[0].nr;
-  } else if (is_cbcmac(aead)) {  // host key setup only, 336 B per key
-    bytes = num_keys * sizeof(CbcKeyDev);
-    host.resize(bytes);
-    CbcKeyDev *h = reinterpret_cast<CbcKeyDev *>(host.data());
-    for (size_t i = 0; i < num_keys; i++) {
-      if (!cbc_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
-        delete km;
-        return nullptr;
-      }
-    }
-    km->nr = (int)h[0].nr;
-  } else if (aead->kind == kAeadAesCtrHmac) {  // host key setup only, 320 B per key
-    bytes = num_keys * sizeof(CtrHmacKeyDev);
-    host.resize(bytes);
-    CtrHmacKeyDev *h = reinterpret_cast<CtrHmacKeyDev *>(host.data());
-    for (size_t i = 0; i < num_keys; i++) {
-      if (!ctr_hmac_key_setup(keys + i * aead->key_len, aead->key_len, &h[i])) {
-        delete km;
-        return nullptr;
-      }
-    }
-    km->nr = (int)h[0].nr;
-  } else if (aead->kind == kAeadTlsCbc) {  // host key setup only, 320 B per key
-    bytes = num_keys * sizeof(TlsCbcKeyDev);
-    host.resize(bytes);
-    TlsCbcKeyDev *h = reinterpret_cast<TlsCbcKeyDev *>(host.data());
-    for (size_t i = 0; i < num_keys; i++) {
-      if (!tls_cbc_key_setup(keys + i * aead->key_len, aead->key_len, tls_cbc_mac_len(aead),
-                             open_only, &h[i])) {
-        delete km;
-        return nullptr;
-      }
-    }
-    km->nr = (int)h[0].nr;
-  } else {
-    bytes = num_keys * sizeof(ChaChaKeyDev);
-    host.resize(bytes);
-    ChaChaKeyDev *h = reinterpret_cast<ChaChaKeyDev *>(host.data());
-    for (size_t i = 0; i < num_keys; i++) chacha_key_setup(keys + i * aead->key_len, &h[i]);
+  // Host key setup: the AEAD's per-key function over the num_keys keys.
+  const size_t key_len = aead->key_len;
+  bool ok;
+  if (gcm)
+    ok = setup_host_keys<GcmKeyDev>(km, keys, host, [&](const uint8_t *k, GcmKeyDev *o) {
+      return gcm_key_setup(k, key_len, o);
+    });
+  else if (is_cbcmac(aead))  // 336 B per key
+    ok = setup_host_keys<CbcKeyDev>(km, keys, host, [&](const uint8_t *k, CbcKeyDev *o) {
+      return cbc_key_setup(k, key_len, o);
+    });
+  else if (aead->kind == kAeadAesCtrHmac)  // 320 B per key
+    ok = setup_host_keys<AesHmacKeyDev>(km, keys, host, [&](const uint8_t *k, AesHmacKeyDev *o) {
+      return ctr_hmac_key_setup(k, key_len, o);
+    });
+  else if (aead->kind == kAeadTlsCbc)
+    ok = setup_host_keys<AesHmacKeyDev>(km, keys, host, [&](const uint8_t *k, AesHmacKeyDev *o) {
+      return tls_cbc_key_setup(k, key_len, tls_cbc_mac_len(aead), open_only, o);
+    });
+  else
+    ok = setup_host_keys<ChaChaKeyDev>(km, keys, host, [&](const uint8_t *k, ChaChaKeyDev *o) {
+      chacha_key_setup(k, o);
+      return true;
+    });
+  if (!ok) {
+    delete km;
+    return nullptr;
   }
+  const size_t bytes = host.size();
   if (hipMalloc(&km->dev, bytes) != hipSuccess) {
     delete km;
     return nullptr;
@@ -363,10 +355,10 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
                        open, km->nr, stream, ev);
     t_timing.last_name = "cbcmac_kernel";
   } else if (km->aead->kind == kAeadAesCtrHmac) {
-    rc = launch_ctr_hmac(static_cast<const CtrHmacKeyDev *>(km->dev), d, open, km->nr, stream, ev);
+    rc = launch_ctr_hmac(static_cast<const AesHmacKeyDev *>(km->dev), d, open, km->nr, stream, ev);
     t_timing.last_name = "ctr_hmac_kernel";
   } else if (km->aead->kind == kAeadTlsCbc) {
-    rc = launch_tls_cbc(static_cast<const TlsCbcKeyDev *>(km->dev), d, tls_cbc_mac_len(km->aead) == 20,
+    rc = launch_tls_cbc(static_cast<const AesHmacKeyDev *>(km->dev), d, tls_cbc_mac_len(km->aead) == 20,
                         open, km->nr, stream, ev);
     t_timing.last_name = "tls_cbc_kernel";
   } else {
@@ -1808,7 +1800,7 @@ int tls_cbc_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *s
       d.max_plain_len = kTlsMaxPlainLen;
     }
     const KernelEvents *ev = timing_pair();
-    ok = launch_tls_cbc(static_cast<const TlsCbcKeyDev *>(st->km->dev), d, mac_len == 20, !t->seal,
+    ok = launch_tls_cbc(static_cast<const AesHmacKeyDev *>(st->km->dev), d, mac_len == 20, !t->seal,
                         st->km->nr, stream, ev) == 0;
     t_timing.last_name = "tls_cbc_kernel";
   }

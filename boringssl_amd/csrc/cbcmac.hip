@@ -17,40 +17,23 @@
 //   keystream one block ahead of the chain.
 // * AES by the bank-replicated T-tables of aes_tables.h: every lane reads its
 //   own bank whatever the (secret) index.
-// * One key: the round keys are wave-uniform (scalar loads).  Keysets: each
-//   lane copies its key's schedule into an LDS slot of its own with an odd
-//   stride in words, so the 64 lanes' reads of word w fall in 64 different
-//   banks.  The workgroup is as large as 160 KiB of LDS allows next to the
-//   64 KiB of tables.
-// * Ragged batches are processed in the order of build_length_order, so the
-//   lanes of a wave run similar trip counts.
+// * The frame around the AEAD -- LDS layout, the lane's record and round keys
+//   (wave-uniform for one key, per-lane LDS slots for keysets), the failed
+//   record's zero-fill, the launcher with the length order of ragged batches
+//   -- is lane_frame.h.
 #include <hip/hip_runtime.h>
 
 #include "aes_tables.h"
 #include "internal.h"
+#include "lane_frame.h"
 #include "rec_blocks.h"
 
 namespace bssl_amd {
 namespace {
 
-// Threads per workgroup and the LDS slot stride (words) of a lane's round keys.
-template <int NR, bool KEYSET>
-struct Shape {
-  static constexpr int kStride = 4 * (NR + 1) + 1;  // odd: 45 or 61
-  static constexpr int kThreads = KEYSET && NR == 14 ? 384 : 512;
-  static constexpr int kSlotWords = KEYSET ? kThreads * kStride : 1;
-};
-
-template <int NR, bool KEYSET>
-struct Lds {
-  uint32_t t[256][2][32];  // T0 / T1, replica (lane & 31)
-  uint32_t slot[Shape<NR, KEYSET>::kSlotWords];
-};
-static_assert(sizeof(Lds<10, true>) <= 160 * 1024 && sizeof(Lds<14, true>) <= 160 * 1024 &&
-                  sizeof(Lds<10, false>) <= 80 * 1024 && sizeof(Lds<14, false>) <= 80 * 1024,
-              "LDS per workgroup (one-key kernels: two workgroups per CU)");
-static_assert(Shape<10, true>::kStride % 2 == 1 && Shape<14, true>::kStride % 2 == 1,
-              "odd slot stride: lane l's word w in bank (l * stride + w) % 64, all different");
+// Threads per workgroup: two workgroups per CU for one key; for keysets as
+// many lanes as 160 KiB of LDS hold slots for (lane_frame.h).
+constexpr int cbcmac_threads(int nr, bool keyset) { return keyset && nr == 14 ? 384 : 512; }
 
 // ---- the two modes -----------------------------------------------------------
 
@@ -112,27 +95,16 @@ __device__ __forceinline__ uint4 ccm_ad_block(const uint8_t *ad, uint64_t ad_len
 // One record per lane.  EAX: AES-EAX, else AES-CCM with L = 2 and M =
 // b.tag_len.
 template <bool EAX, bool OPEN, int NR, bool KEYSET>
-__global__ __launch_bounds__((Shape<NR, KEYSET>::kThreads)) void cbcmac_kernel(
+__global__ __launch_bounds__((cbcmac_threads(NR, KEYSET))) void cbcmac_kernel(
     const CbcKeyDev *__restrict__ keys, BatchDesc b) {
-  using S = Shape<NR, KEYSET>;
-  __shared__ Lds<NR, KEYSET> L;
-  for (int e = threadIdx.x; e < 256 * 64; e += S::kThreads) {
-    const uint32_t v = kAesTables.te0[e >> 6];
-    (&L.t[0][0][0])[e] = ((e >> 5) & 1) ? rotl(v, 8) : v;
-  }
-  const uint64_t pos = (uint64_t)blockIdx.x * S::kThreads + threadIdx.x;
-  const bool active = pos < b.num_records;
-  const uint64_t rec = active ? (b.order ? (uint64_t)b.order[pos] : pos) : 0;
-  uint64_t off = 0, len = 0, ad_off = 0, ad_len = 0;
-  uint32_t kidx = 0;
-  bool live = active;
+  constexpr int kThreads = cbcmac_threads(NR, KEYSET);
+  __shared__ LaneLds<NR, KEYSET, kThreads> L;
+  lane_fill_tables(L, kAesTables.te0, kThreads);
+  const LaneRecord r = lane_record<KEYSET>(b, kThreads);
+  const bool active = r.active;
+  const uint64_t rec = r.rec, off = r.off, len = r.len, ad_off = r.ad_off, ad_len = r.ad_len;
+  bool live = r.live;
   if (active) {
-    off = meta<uint64_t>(b.offsets, rec, rec * b.record_stride);
-    len = meta<uint64_t>(b.lengths, rec, b.record_len);
-    ad_off = meta<uint64_t>(b.ad_offsets, rec, rec * b.ad_stride);
-    ad_len = meta<uint64_t>(b.ad_lengths, rec, b.ad_len);
-    if (KEYSET) kidx = meta<uint32_t>(b.key_index, rec, 0u);
-    live = kidx < b.num_keys && meta<uint8_t>(b.valid, rec, 1) != 0;
     // e_aesccm.cc.inc:71-78, 188-191; e_aeseax.cc:76, 234, 276-284.
     if (EAX)
       live = live && b.tag_len == 16 && (b.nonce_len == 12 || b.nonce_len == 16);
@@ -140,15 +112,8 @@ __global__ __launch_bounds__((Shape<NR, KEYSET>::kThreads)) void cbcmac_kernel(
       live = live && b.nonce_len == 13 && len <= kCcmMaxInput && b.tag_len >= 4 &&
              b.tag_len <= 16 && (b.tag_len & 1) == 0;
   }
-  // Round keys: the key's own (global, wave-uniform) or the lane's LDS slot.
-  const CbcKeyDev &K = keys[live ? kidx : 0];
-  const uint32_t *rk = &K.rk[0][0];
-  if constexpr (KEYSET) {
-    uint32_t *slot = &L.slot[threadIdx.x * S::kStride];
-    for (int w = 0; w < 4 * (NR + 1); w++) slot[w] = rk[w];
-    rk = slot;
-  }
-  __syncthreads();
+  const CbcKeyDev &K = keys[live ? r.kidx : 0];
+  const uint32_t *rk = lane_round_keys<NR, KEYSET>(&K.rk[0][0], L);
 
   const uint32_t M = b.tag_len;
   const uint8_t *src = b.in + off;
@@ -268,65 +233,28 @@ __global__ __launch_bounds__((Shape<NR, KEYSET>::kThreads)) void cbcmac_kernel(
       store_block(tagp, tag, M);
     }
   }
-  if (!active) return;
-  if (b.status) b.status[rec] = ok ? 1 : 0;
-  if (!ok) {
-    // A failed record's output (and the tag of a failed seal) zero-filled
-    // (aead.cc.inc:132-139, 539-547): a second pass over this record only.
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    for (uint64_t o = 0; o < len; o += 16) store_block(dst + o, z, len - o < 16 ? (uint32_t)(len - o) : 16u);
-    if (!OPEN) store_block(tagp, z, M < 16 ? M : 16u);
-  }
-}
-
-template <bool EAX, bool OPEN, int NR, bool KEYSET>
-void launch_one(const CbcKeyDev *keys, const BatchDesc &b, hipStream_t s) {
-  constexpr unsigned threads = Shape<NR, KEYSET>::kThreads;
-  const unsigned grid = (unsigned)((b.num_records + threads - 1) / threads);
-  hipLaunchKernelGGL((cbcmac_kernel<EAX, OPEN, NR, KEYSET>), dim3(grid), dim3(threads), 0, s, keys,
-                     b);
-}
-
-template <bool EAX, bool OPEN>
-void launch_mode(const CbcKeyDev *keys, const BatchDesc &b, int nr, hipStream_t s) {
-  const bool keyset = b.key_index != nullptr;
-  if (nr == 14)
-    keyset ? launch_one<EAX, OPEN, 14, true>(keys, b, s) : launch_one<EAX, OPEN, 14, false>(keys, b, s);
-  else
-    keyset ? launch_one<EAX, OPEN, 10, true>(keys, b, s) : launch_one<EAX, OPEN, 10, false>(keys, b, s);
+  if (active) lane_finish<OPEN>(b, rec, ok, len, dst, M < 16 ? M : 16u);
 }
 
 }  // namespace
 
 int launch_cbcmac(const CbcKeyDev *keys, const BatchDesc &b, bool eax, bool open, int nr,
                   void *stream, const KernelEvents *ev) {
-  if (b.extra || b.extra_len || b.iovecs) return 1;  // not supported by these AEADs' kernel
-  if (nr != 10 && nr != 14) return 1;
-  if (b.num_records == 0) return 0;
-  if ((b.num_records + 383) / 384 > 0x7fffffffu) return 1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  BatchDesc bo = b;  // with the processing order of a ragged batch
-  uint32_t *order = nullptr;
-  if (wants_length_order(b)) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
-                       s) != hipSuccess)
-      return 2;
-    const int orc = build_length_order(b.lengths, b.num_records, order, order + b.num_records, s);
-    if (orc) {
-      hipFreeAsync(order, s);
-      return orc;
-    }
-    bo.order = order;
-  }
-  if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->start), s);
-  if (eax)
-    open ? launch_mode<true, true>(keys, bo, nr, s) : launch_mode<true, false>(keys, bo, nr, s);
-  else
-    open ? launch_mode<false, true>(keys, bo, nr, s) : launch_mode<false, false>(keys, bo, nr, s);
-  const int rc = (int)hipGetLastError();
-  if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  if (order) hipFreeAsync(order, s);
-  return rc;
+  const bool keyset = b.key_index != nullptr;
+  return launch_lane_kernel(
+      b, nr == 10 || nr == 14, cbcmac_threads(nr, keyset), /*half_rule=*/false, stream, ev,
+      [&](const BatchDesc &bo, unsigned grid, unsigned threads, hipStream_t s) {
+        with_nr_keyset(nr, keyset, [&](auto NR, auto KEYSET) {
+          auto go = [&](auto EAX, auto OPEN) {
+            hipLaunchKernelGGL((cbcmac_kernel<EAX.value, OPEN.value, NR.value, KEYSET.value>),
+                               dim3(grid), dim3(threads), 0, s, keys, bo);
+          };
+          if (eax)
+            open ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+          else
+            open ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
+        });
+      });
 }
 
 }  // namespace bssl_amd

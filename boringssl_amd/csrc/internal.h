@@ -13,11 +13,10 @@
 //   ChaChaKeyDev one per ChaCha20-Poly1305 key (32 bytes).
 //   CbcKeyDev   one per AES-CCM / AES-EAX key (336 bytes): the plain round
 //               keys and EAX's per-key constants (cbcmac.hip).
-//   CtrHmacKeyDev one per AES-CTR-HMAC-SHA256 key (320 bytes): the plain round
-//               keys and HMAC's inner and outer SHA-256 states (ctr_hmac.hip).
-//   TlsCbcKeyDev one per TLS AES-CBC-HMAC key (320 bytes): the round keys of
-//               the context's direction and HMAC's inner and outer SHA-1 or
-//               SHA-256 states (tls_cbc.hip).
+//   AesHmacKeyDev one per AES-CTR-HMAC-SHA256 or TLS AES-CBC-HMAC key (320
+//               bytes): the round keys (TLS: of the context's direction) and
+//               HMAC's inner and outer SHA-1 or SHA-256 states (ctr_hmac.hip,
+//               tls_cbc.hip).
 //   BatchDesc   the record-batch descriptor passed by value to the kernels.
 #ifndef BSSL_AMD_INTERNAL_H
 #define BSSL_AMD_INTERNAL_H
@@ -81,35 +80,23 @@ struct alignas(16) CbcKeyDev {
 };
 static_assert(sizeof(CbcKeyDev) == 240 + 16 + 32 + 48, "layout");
 
-// One per AES-128/256-CTR-HMAC-SHA256 key (320 bytes; ctr_hmac.hip): the
-// FIPS-197 schedule of the AES half of the key as little-endian words,
-// unrotated, and the SHA-256 states of hmac_init
-// (crypto/cipher/e_aesctrhmac.cc:52-74) after the block (HMAC key || 0^32) XOR
-// 0x36.. (inner) and XOR 0x5c.. (outer), as FIPS 180-4's words H0..H7.
-struct alignas(16) CtrHmacKeyDev {
+// One per key of the AEADs that pair AES with HMAC (320 bytes):
+// AES-128/256-CTR-HMAC-SHA256 (ctr_hmac.hip; the key is AES key || HMAC key,
+// crypto/cipher/e_aesctrhmac.cc:52-109) and TLS AES-CBC-HMAC-SHA1/SHA256
+// (tls_cbc.hip; MAC key || AES key, e_tls.cc:75-96).  rk: the FIPS-197
+// schedule of the AES key as little-endian words, unrotated -- or, for an
+// opening TLS context, the schedule of the equivalent inverse cipher (FIPS-197
+// 5.3.5: the round keys in reverse order, InvMixColumns applied to rounds
+// 1..nr-1).  inner / outer: HMAC's states after the block (MAC key || zeros)
+// XOR 0x36.. / 0x5c.., as FIPS 180-4's words (SHA-1 uses the first five).
+struct alignas(16) AesHmacKeyDev {
   uint32_t rk[15][4];
   uint32_t nr;
   uint32_t pad[3];
   uint32_t inner[8];
   uint32_t outer[8];
 };
-static_assert(sizeof(CtrHmacKeyDev) == 240 + 16 + 32 + 32, "layout");
-
-// One per TLS AES-CBC-HMAC-SHA1/SHA256 key (320 bytes; tls_cbc.hip).  The key
-// is MAC key || AES key (e_tls.cc:75-96).  rk: for a sealing context the
-// FIPS-197 schedule as little-endian words; for an opening one the schedule of
-// the equivalent inverse cipher (FIPS-197 5.3.5: the round keys in reverse
-// order, InvMixColumns applied to rounds 1..nr-1).  inner / outer: HMAC's
-// states after the block (MAC key || zeros) XOR 0x36.. / 0x5c.., as FIPS
-// 180-4's words (SHA-1 uses the first five).
-struct alignas(16) TlsCbcKeyDev {
-  uint32_t rk[15][4];
-  uint32_t nr;
-  uint32_t pad[3];
-  uint32_t inner[8];
-  uint32_t outer[8];
-};
-static_assert(sizeof(TlsCbcKeyDev) == 240 + 16 + 32 + 32, "layout");
+static_assert(sizeof(AesHmacKeyDev) == 240 + 16 + 32 + 32, "layout");
 
 enum AeadKind : int {
   kAeadAesGcm = 0,
@@ -293,7 +280,7 @@ int launch_cbcmac(const CbcKeyDev *keys, const BatchDesc &b, bool eax, bool open
 // AES-128/256-CTR-HMAC-SHA256 (ctr_hmac.hip), one lane per record; tag_len 1
 // to 32.  BatchDesc::extra and ::iovecs are not supported (error 1); ::done is
 // never written.
-int launch_ctr_hmac(const CtrHmacKeyDev *keys, const BatchDesc &b, bool open, int nr, void *stream,
+int launch_ctr_hmac(const AesHmacKeyDev *keys, const BatchDesc &b, bool open, int nr, void *stream,
                     const KernelEvents *ev);
 // The TLS AES-CBC-HMAC AEADs (tls_cbc.hip), one lane per record.  sha1: the
 // MAC is HMAC-SHA1 (20 bytes), else HMAC-SHA256 (32); tag_len is the tag slot
@@ -302,7 +289,7 @@ int launch_ctr_hmac(const CtrHmacKeyDev *keys, const BatchDesc &b, bool open, in
 // Open: `keys` hold equivalent-inverse schedules, the records are whole wire
 // fragments, `tags` is unused.  BatchDesc::extra and ::iovecs are not
 // supported (error 1); ::done is never written.
-int launch_tls_cbc(const TlsCbcKeyDev *keys, const BatchDesc &b, bool sha1, bool open, int nr,
+int launch_tls_cbc(const AesHmacKeyDev *keys, const BatchDesc &b, bool sha1, bool open, int nr,
                    void *stream, const KernelEvents *ev);
 // Its message limit: the 32-bit block counter (e_aesctrhmac.cc:190, 226).
 constexpr uint64_t kCtrHmacMaxInput = (uint64_t(1) << 36) - 1;
@@ -420,12 +407,12 @@ void chacha_key_setup(const uint8_t *key, ChaChaKeyDev *out);
 bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out);
 // AES-CTR-HMAC-SHA256 key, AES key || 32-byte HMAC key (host only); false for
 // a bad key length.
-bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out);
+bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, AesHmacKeyDev *out);
 // TLS AES-CBC-HMAC key, MAC key (mac_len: 20 or 32 bytes) || AES key (host
 // only); open: the schedule of the equivalent inverse cipher.  false for a bad
 // key length.
 bool tls_cbc_key_setup(const uint8_t *key, size_t key_len, size_t mac_len, bool open,
-                       TlsCbcKeyDev *out);
+                       AesHmacKeyDev *out);
 // Key counts from which make_keys builds AES-GCM tables on the device.
 constexpr size_t kDeviceKeySetupMin = 64;
 

@@ -36,6 +36,20 @@ void eax_dbl(const uint32_t in[4], uint32_t out[4]) {
   secure_zero(be, sizeof(be));
 }
 
+// The key's FIPS-197 schedule into rk (60 words, which the caller wipes) and,
+// as little-endian words, unrotated, into the zeroed *out with its nr.
+// Returns nr, or 0 for a bad key length (*out untouched).
+template <class KeyDev>
+int expand_into(const uint8_t *key, size_t key_len, uint32_t (&rk)[60], KeyDev *out) {
+  const int nr = ks_expand(key, (int)key_len, rk);
+  if (!nr) return 0;
+  memset(out, 0, sizeof(*out));
+  for (int r = 0; r <= nr; r++)
+    for (int c = 0; c < 4; c++) out->rk[r][c] = rk[4 * r + c];
+  out->nr = (uint32_t)nr;
+  return nr;
+}
+
 }  // namespace
 
 // aead_aes_ccm_init / aead_aes_eax_init (e_aesccm.cc.inc:275-308,
@@ -43,12 +57,8 @@ void eax_dbl(const uint32_t in[4], uint32_t out[4]) {
 // (computed for CCM keys too; nothing reads them there).
 bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out) {
   uint32_t rk[60];
-  const int nr = ks_expand(key, (int)key_len, rk);
+  const int nr = expand_into(key, key_len, rk, out);
   if (!nr) return false;
-  memset(out, 0, sizeof(*out));
-  for (int r = 0; r <= nr; r++)
-    for (int c = 0; c < 4; c++) out->rk[r][c] = rk[4 * r + c];
-  out->nr = (uint32_t)nr;
   uint32_t l[4] = {0, 0, 0, 0};
   ks_encrypt(rk, nr, l);
   eax_dbl(l, out->eax_b);
@@ -96,37 +106,6 @@ void sha256_block(uint32_t h[8], const uint8_t blk[64]) {
   secure_zero(v, sizeof(v));
 }
 
-}  // namespace
-
-// aead_aes_ctr_hmac_sha256_init (crypto/cipher/e_aesctrhmac.cc:76-109): the
-// schedule of the AES key and hmac_init's two states (:52-74), each one
-// compression from SHA-256's initial value (FIPS 180-4 5.3.3) over the HMAC
-// key XOR the pad byte, the rest of the block the pad byte itself.
-bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, CtrHmacKeyDev *out) {
-  if (key_len != 48 && key_len != 64) return false;
-  const size_t aes_len = key_len - 32;
-  uint32_t rk[60];
-  const int nr = ks_expand(key, (int)aes_len, rk);
-  if (!nr) return false;
-  memset(out, 0, sizeof(*out));
-  for (int r = 0; r <= nr; r++)
-    for (int c = 0; c < 4; c++) out->rk[r][c] = rk[4 * r + c];
-  out->nr = (uint32_t)nr;
-  uint8_t blk[64];
-  for (int pass = 0; pass < 2; pass++) {
-    const uint8_t pad = pass ? 0x5c : 0x36;
-    for (int i = 0; i < 64; i++) blk[i] = (uint8_t)((i < 32 ? key[aes_len + i] : 0) ^ pad);
-    uint32_t *h = pass ? out->outer : out->inner;
-    for (int i = 0; i < 8; i++) h[i] = kSha256Init[i];
-    sha256_block(h, blk);
-  }
-  secure_zero(blk, sizeof(blk));
-  secure_zero(rk, sizeof(rk));
-  return true;
-}
-
-namespace {
-
 // FIPS 180-4 6.1.2: one SHA-1 compression of the 64-byte block `blk` into the
 // state h.  Plain and slow, as sha256_block.
 void sha1_block(uint32_t h[5], const uint8_t blk[64]) {
@@ -160,41 +139,57 @@ uint32_t inv_mix_column(uint32_t a) {
   return a1 ^ ks_rotr8(a, 2) ^ ks_rotr8(a, 3) ^ ks_xtime4(a ^ a1);
 }
 
-}  // namespace
-
-// aead_tls_init (crypto/cipher/e_tls.cc:61-103): the key is MAC key || AES key;
-// HMAC's two states as for ctr_hmac_key_setup, over SHA-1 (mac_len 20) or
-// SHA-256 (32).  An opening context decrypts: its schedule is the one of the
-// equivalent inverse cipher (FIPS-197 5.3.5).
-bool tls_cbc_key_setup(const uint8_t *key, size_t key_len, size_t mac_len, bool open,
-                       TlsCbcKeyDev *out) {
-  if ((mac_len != 20 && mac_len != 32) || key_len <= mac_len) return false;
-  uint32_t rk[60];
-  const int nr = ks_expand(key + mac_len, (int)(key_len - mac_len), rk);
-  if (!nr) return false;
-  memset(out, 0, sizeof(*out));
-  for (int r = 0; r <= nr; r++)
-    for (int c = 0; c < 4; c++) {
-      const uint32_t w = rk[4 * (open ? nr - r : r) + c];
-      out->rk[r][c] = open && r > 0 && r < nr ? inv_mix_column(w) : w;
-    }
-  out->nr = (uint32_t)nr;
+// HMAC's two states for a MAC key of mac_len (<= 64) bytes (hmac_init,
+// e_aesctrhmac.cc:52-74; HMAC_Init_ex for e_tls.cc): each one compression from
+// the hash's initial value (FIPS 180-4 5.3.1, 5.3.3) over the key XOR the pad
+// byte, the rest of the block the pad byte itself.  sha1: SHA-1, which uses the
+// first five words; else SHA-256.
+void hmac_states(const uint8_t *mac_key, size_t mac_len, bool sha1, uint32_t (&inner)[8],
+                 uint32_t (&outer)[8]) {
+  static const uint32_t kSha1Init[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u,
+                                        0xc3d2e1f0u};
   uint8_t blk[64];
   for (int pass = 0; pass < 2; pass++) {
     const uint8_t pad = pass ? 0x5c : 0x36;
-    for (size_t i = 0; i < 64; i++) blk[i] = (uint8_t)((i < mac_len ? key[i] : 0) ^ pad);
-    uint32_t *h = pass ? out->outer : out->inner;
-    if (mac_len == 20) {
-      static const uint32_t kSha1Init[5] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u,
-                                            0xc3d2e1f0u};
-      for (int i = 0; i < 5; i++) h[i] = kSha1Init[i];
-      sha1_block(h, blk);
-    } else {
-      for (int i = 0; i < 8; i++) h[i] = kSha256Init[i];
-      sha256_block(h, blk);
-    }
+    for (size_t i = 0; i < 64; i++) blk[i] = (uint8_t)((i < mac_len ? mac_key[i] : 0) ^ pad);
+    uint32_t *h = pass ? outer : inner;
+    for (int i = 0; i < (sha1 ? 5 : 8); i++) h[i] = sha1 ? kSha1Init[i] : kSha256Init[i];
+    sha1 ? sha1_block(h, blk) : sha256_block(h, blk);
   }
   secure_zero(blk, sizeof(blk));
+}
+
+}  // namespace
+
+// aead_aes_ctr_hmac_sha256_init (crypto/cipher/e_aesctrhmac.cc:76-109): the
+// key is AES key || 32-byte HMAC key; the schedule and HMAC-SHA256's states.
+bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, AesHmacKeyDev *out) {
+  if (key_len != 48 && key_len != 64) return false;
+  const size_t aes_len = key_len - 32;
+  uint32_t rk[60];
+  if (!expand_into(key, aes_len, rk, out)) return false;
+  hmac_states(key + aes_len, 32, false, out->inner, out->outer);
+  secure_zero(rk, sizeof(rk));
+  return true;
+}
+
+// aead_tls_init (crypto/cipher/e_tls.cc:61-103): the key is MAC key || AES key;
+// HMAC's states over SHA-1 (mac_len 20) or SHA-256 (32).  An opening context
+// decrypts: its schedule is the one of the equivalent inverse cipher (FIPS-197
+// 5.3.5).
+bool tls_cbc_key_setup(const uint8_t *key, size_t key_len, size_t mac_len, bool open,
+                       AesHmacKeyDev *out) {
+  if ((mac_len != 20 && mac_len != 32) || key_len <= mac_len) return false;
+  uint32_t rk[60];
+  const int nr = expand_into(key + mac_len, key_len - mac_len, rk, out);
+  if (!nr) return false;
+  if (open)
+    for (int r = 0; r <= nr; r++)
+      for (int c = 0; c < 4; c++) {
+        const uint32_t w = rk[4 * (nr - r) + c];
+        out->rk[r][c] = r > 0 && r < nr ? inv_mix_column(w) : w;
+      }
+  hmac_states(key, mac_len, mac_len == 20, out->inner, out->outer);
   secure_zero(rk, sizeof(rk));
   return true;
 }

@@ -1,6 +1,7 @@
-// rec_blocks.h -- what the one-lane-per-record kernels (cbcmac.hip,
-// ctr_hmac.hip) share: N blocks through the T-table AES of aes_tables.h
-// together, and 16-byte blocks of records that start at any byte offset.
+// rec_blocks.h -- the blocks of the one-lane-per-record kernels (cbcmac.hip,
+// ctr_hmac.hip, tls_cbc.hip): N blocks through the T-table AES of aes_tables.h
+// together, and 16-byte blocks of records that start at any byte offset.  The
+// frame those kernels share around their AEADs is lane_frame.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,6 +52,11 @@ __device__ __forceinline__ void aes_n(uint4 (&s)[N], const uint32_t *rk, const L
 }
 
 // ---- record buffers: blocks as little-endian words of their bytes -----------
+
+// min(16, the bytes of [0, total) from `at` on).
+__device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {
+  return at >= total ? 0u : total - at < 16 ? (uint32_t)(total - at) : 16u;
+}
 
 // The first n bytes of v (n <= 16), the rest zero.
 __device__ __forceinline__ uint4 mask_block(uint4 v, uint32_t n) {

@@ -58,6 +58,34 @@ __device__ __forceinline__ void to_schedule(const uint4 (&v)[4], uint32_t (&w)[1
   }
 }
 
+// SHA's padding (FIPS 180-4 5.1.1) of a message of `total` bytes, in its block
+// w at byte offset `base`: 0x80 after the last byte where that falls into this
+// block (the bytes past the message are zero already), and in the message's
+// last block (`last`) its length `bits` at the end.
+__device__ __forceinline__ void sha_padding(uint32_t (&w)[16], uint64_t total, uint64_t base,
+                                            bool last, uint64_t bits) {
+  if (total >= base && total - base < 64) {
+    const uint32_t r = (uint32_t)(total - base);
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] |= (r >> 2) == (uint32_t)i ? 0x80000000u >> (8 * (r & 3)) : 0u;
+  }
+  if (last) {
+    w[14] = (uint32_t)(bits >> 32);
+    w[15] = (uint32_t)bits;
+  }
+}
+
+// HMAC's outer block (RFC 2104): the inner digest (WORDS words: 5 for SHA-1,
+// 8 for SHA-256) with SHA's padding; the opad block counts in the length.  The
+// caller restarts its state from the key's outer state.
+template <int WORDS>
+__device__ __forceinline__ void hmac_outer_block(const uint32_t (&inner)[8], uint32_t (&w)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; i++) w[i] = i < WORDS ? inner[i] : 0;
+  w[WORDS] = 0x80000000u;
+  w[15] = 8 * (64 + 4 * WORDS);
+}
+
 // SHA-1 (FIPS 180-4 6.1.2): h[0..5) += the 80 rounds over the block w, used
 // up as above.  (h has eight words so both hashes share their callers; SHA-1
 // leaves the last three alone.)

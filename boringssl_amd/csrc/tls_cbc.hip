@@ -14,7 +14,9 @@
 // pad_len bytes) to the record's tag slot; open takes the whole wire.
 // Design:
 // * Neither the CBC-encrypt chain nor the hash chain of a record can be
-//   split: one lane per record, as in ctr_hmac.hip.
+//   split: one lane per record, in the frame of lane_frame.h (DESIGN.md
+//   4.11a): LDS layout, the lane's record and round keys, the failed record's
+//   zero-fill, the launcher with the length order of ragged batches.
 // * One loop per record over the 64-byte blocks of the hash.  The hash stream
 //   is 13 bytes ahead of the record's 16-byte blocks; a step builds its hash
 //   block from the previous step's last record block (kept in registers) and
@@ -30,41 +32,27 @@
 //   depends on the padding byte is done by masks only -- see "constant shape"
 //   at tls_cbc_kernel.
 // * One key: the round keys and both HMAC states are wave-uniform.  Keysets:
-//   round keys in per-lane LDS slots with an odd stride in words.
-// * Ragged batches are processed in the order of build_length_order.
+//   round keys in the frame's per-lane LDS slots.
 #include <hip/hip_runtime.h>
 
 #include "aes_inv_tables.h"
 #include "aes_tables.h"
 #include "internal.h"
+#include "lane_frame.h"
 #include "rec_blocks.h"
 #include "sha_compress.h"
 
 namespace bssl_amd {
 namespace {
 
-// Threads per workgroup and the LDS slot stride of a lane's round keys, as in
-// ctr_hmac.hip.  One key: the AES-128 seal kernels take at most 128 VGPRs,
-// four waves per SIMD as two workgroups of eight waves; the others (131 to
-// 156 VGPRs) three, as one workgroup of twelve.  Keysets: as large as 160 KiB
-// of LDS allows.
-template <bool OPEN, int NR, bool KEYSET>
-struct Shape {
-  static constexpr int kStride = 4 * (NR + 1) + 1;  // odd: 45 or 61
-  static constexpr int kThreads = !KEYSET ? (OPEN || NR == 14 ? 768 : 512) : NR == 14 ? 384 : 512;
-  static constexpr int kSlotWords = KEYSET ? kThreads * kStride : 1;
-};
-
-template <int NR, bool KEYSET>
-struct Lds {
-  uint32_t t[256][2][32];  // T0 / T1 (seal) or Td0 / Td1 (open), replica (lane & 31)
-  uint32_t slot[Shape<false, NR, KEYSET>::kSlotWords];  // (keysets: the same for open)
-};
-static_assert(sizeof(Lds<10, true>) <= 160 * 1024 && sizeof(Lds<14, true>) <= 160 * 1024 &&
-                  sizeof(Lds<10, false>) <= 80 * 1024 && sizeof(Lds<14, false>) <= 80 * 1024,
-              "LDS per workgroup");
-static_assert(Shape<false, 10, true>::kStride % 2 == 1 && Shape<false, 14, true>::kStride % 2 == 1,
-              "odd slot stride: lane l's word w in bank (l * stride + w) % 64, all different");
+// Threads per workgroup (the largest: small one-key batches take half,
+// launch_lane_kernel's half_rule, so the kernel reads blockDim.x).  One key:
+// the AES-128 seal kernels take at most 128 VGPRs, four waves per SIMD as two
+// workgroups of eight waves; the others (131 to 156 VGPRs) three, as one
+// workgroup of twelve.  Keysets: as large as 160 KiB of LDS allows.
+constexpr int tls_cbc_threads(bool open, int nr, bool keyset) {
+  return !keyset ? (open || nr == 14 ? 768 : 512) : nr == 14 ? 384 : 512;
+}
 
 template <bool SHA1>
 struct Mac {
@@ -139,11 +127,6 @@ __device__ __forceinline__ void hash_block(uint4 carry, const uint4 (&v)[4], uin
   for (int i = 0; i < 16; i++) w[i] = __builtin_bswap32(__builtin_amdgcn_alignbyte(f[i + 1], f[i], 3));
 }
 
-// min(16, the bytes of [0, total) from `at` on).
-__device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {
-  return at >= total ? 0u : total - at < 16 ? (uint32_t)(total - at) : 16u;
-}
-
 // One record per lane.
 //
 // Constant shape of OPEN (Lucky 13): every trip count, every
@@ -155,44 +138,26 @@ __device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {
 // `kmin`, `jtrail`, `dist*` and `cap` (the record layer's plaintext limit) are
 // public; `p`, `padlen`, `dlen`, `bad`, `macacc`, `dig`, `over` are not.
 template <bool OPEN, int NR, bool SHA1, bool KEYSET>
-__global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_kernel(
-    const TlsCbcKeyDev *__restrict__ keys, BatchDesc b) {
-  using S = Shape<OPEN, NR, KEYSET>;
+__global__ __launch_bounds__((tls_cbc_threads(OPEN, NR, KEYSET))) void tls_cbc_kernel(
+    const AesHmacKeyDev *__restrict__ keys, BatchDesc b) {
   using H = Mac<SHA1>;
   constexpr uint32_t M = H::kLen;
-  __shared__ Lds<NR, KEYSET> L;
-  for (int e = threadIdx.x; e < 256 * 64; e += blockDim.x) {
-    const uint32_t v = OPEN ? kAesInvTables.td0[e >> 6] : kAesTables.te0[e >> 6];
-    (&L.t[0][0][0])[e] = ((e >> 5) & 1) ? rotl(v, 8) : v;
-  }
-  const uint64_t pos = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = pos < b.num_records;
-  const uint64_t rec = active ? (b.order ? (uint64_t)b.order[pos] : pos) : 0;
-  uint64_t off = 0, len = 0, ad_off = 0, ad_len = 0;
-  uint32_t kidx = 0;
-  bool live = active;
+  // T0 / T1 (seal) or Td0 / Td1 (open).
+  __shared__ LaneLds<NR, KEYSET, tls_cbc_threads(OPEN, NR, KEYSET)> L;
+  lane_fill_tables(L, OPEN ? kAesInvTables.td0 : kAesTables.te0, blockDim.x);
+  const LaneRecord r = lane_record<KEYSET>(b, blockDim.x);
+  const bool active = r.active;
+  const uint64_t rec = r.rec, off = r.off, len = r.len, ad_off = r.ad_off, ad_len = r.ad_len;
+  // e_tls.cc:137-146, 281-295; open: a length that is no multiple of the
+  // block or below the MAC and the padding length byte (:315-319,
+  // tls_cbc.cc:37-39).
+  bool live = r.live;
   if (active) {
-    off = meta<uint64_t>(b.offsets, rec, rec * b.record_stride);
-    len = meta<uint64_t>(b.lengths, rec, b.record_len);
-    ad_off = meta<uint64_t>(b.ad_offsets, rec, rec * b.ad_stride);
-    ad_len = meta<uint64_t>(b.ad_lengths, rec, b.ad_len);
-    if (KEYSET) kidx = meta<uint32_t>(b.key_index, rec, 0u);
-    // e_tls.cc:137-146, 281-295; open: a length that is no multiple of the
-    // block or below the MAC and the padding length byte (:315-319,
-    // tls_cbc.cc:37-39).
-    live = kidx < b.num_keys && meta<uint8_t>(b.valid, rec, 1) != 0 && b.nonce_len == 16 &&
-           ad_len == 11 && b.tag_len == H::kSlot;
+    live = live && b.nonce_len == 16 && ad_len == 11 && b.tag_len == H::kSlot;
     if (OPEN) live = live && (len & 15) == 0 && len >= M + 1;
   }
-  // Round keys: the key's own (global, wave-uniform) or the lane's LDS slot.
-  const TlsCbcKeyDev &K = keys[live ? kidx : 0];
-  const uint32_t *rk = &K.rk[0][0];
-  if constexpr (KEYSET) {
-    uint32_t *slot = &L.slot[threadIdx.x * S::kStride];
-    for (int w = 0; w < 4 * (NR + 1); w++) slot[w] = rk[w];
-    rk = slot;
-  }
-  __syncthreads();
+  const AesHmacKeyDev &K = keys[live ? r.kidx : 0];
+  const uint32_t *rk = lane_round_keys<NR, KEYSET>(&K.rk[0][0], L);
 
   const uint8_t *src = b.in + off;
   uint8_t *dst = b.out + off;
@@ -207,10 +172,7 @@ __global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_k
     // The outer hash's block: the inner digest with SHA's padding; h restarts
     // from the state after the opad block.
     auto outer_block = [&](const uint32_t (&inner)[8], uint32_t (&w)[16]) {
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = i < H::kWords ? inner[i] : 0;
-      w[H::kWords] = 0x80000000u;
-      w[15] = 8 * (64 + M);
+      hmac_outer_block<H::kWords>(inner, w);
 #pragma unroll
       for (int i = 0; i < 8; i++) h[i] = K.outer[i];
     };
@@ -264,17 +226,7 @@ __global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_k
           }
           hash_block(carry, v, w);
           carry = v[3];
-          // SHA's padding: 0x80 after the last byte, the length in bits at the
-          // end of the last block.
-          if (hlen >= base && hlen - base < 64) {
-            const uint32_t r = (uint32_t)(hlen - base);
-#pragma unroll
-            for (int i = 0; i < 16; i++) w[i] |= (r >> 2) == (uint32_t)i ? 0x80000000u >> (8 * (r & 3)) : 0u;
-          }
-          if (t + 1 == nM) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-          }
+          sha_padding(w, hlen, base, t + 1 == nM, bits);
           // The whole blocks through the chain; the partial one waits for the MAC.
 #pragma unroll
           for (int k = 0; k < 4; k++) {
@@ -425,71 +377,31 @@ __global__ __launch_bounds__((Shape<OPEN, NR, KEYSET>::kThreads)) void tls_cbc_k
     }
   }
   if (!active) return;
-  if (b.status) b.status[rec] = ok ? 1 : 0;
   if (OPEN && b.out_lengths) b.out_lengths[rec] = ok ? dlen : 0;
-  if (!ok) {
-    // A failed record's output (and the tag slot of a failed seal) zero-filled
-    // (aead.cc.inc:132-139, 368-376): a second pass over this record only.
-    for (uint64_t o = 0; o < len; o += 16) store_block(dst + o, zero, len - o < 16 ? (uint32_t)(len - o) : 16u);
-    if (!OPEN) {
-      uint8_t *tagp = batch_tag(b, rec);
-      for (uint32_t o = 0; o < H::kSlot; o += 16) store_block(tagp + o, zero, H::kSlot - o < 16 ? H::kSlot - o : 16u);
-    }
-  }
-}
-
-template <bool OPEN, int NR, bool SHA1, bool KEYSET>
-void launch_one(const TlsCbcKeyDev *keys, const BatchDesc &b, hipStream_t s) {
-  unsigned threads = Shape<OPEN, NR, KEYSET>::kThreads;
-  // One key: a batch too small to give every CU a full workgroup takes
-  // workgroups of half the size, on twice as many CUs (ctr_hmac.hip).
-  if (!KEYSET && b.num_records < (uint64_t)threads * (uint64_t)device_cu_count()) threads /= 2;
-  const unsigned grid = (unsigned)((b.num_records + threads - 1) / threads);
-  hipLaunchKernelGGL((tls_cbc_kernel<OPEN, NR, SHA1, KEYSET>), dim3(grid), dim3(threads), 0, s, keys, b);
-}
-
-template <bool OPEN, int NR, bool SHA1>
-void launch_keys(const TlsCbcKeyDev *keys, const BatchDesc &b, hipStream_t s) {
-  b.key_index ? launch_one<OPEN, NR, SHA1, true>(keys, b, s)
-              : launch_one<OPEN, NR, SHA1, false>(keys, b, s);
-}
-
-template <bool OPEN>
-void launch_mode(const TlsCbcKeyDev *keys, const BatchDesc &b, bool sha1, int nr, hipStream_t s) {
-  if (nr == 14)
-    launch_keys<OPEN, 14, true>(keys, b, s);  // AES-256 comes with SHA-1 only
-  else
-    sha1 ? launch_keys<OPEN, 10, true>(keys, b, s) : launch_keys<OPEN, 10, false>(keys, b, s);
+  lane_finish<OPEN>(b, rec, ok, len, dst, H::kSlot);
 }
 
 }  // namespace
 
-int launch_tls_cbc(const TlsCbcKeyDev *keys, const BatchDesc &b, bool sha1, bool open, int nr,
+int launch_tls_cbc(const AesHmacKeyDev *keys, const BatchDesc &b, bool sha1, bool open, int nr,
                    void *stream, const KernelEvents *ev) {
-  if (b.extra || b.extra_len || b.iovecs) return 1;  // not supported by these AEADs' kernel
-  if ((nr != 10 && nr != 14) || (nr == 14 && !sha1)) return 1;
-  if (b.num_records == 0) return 0;
-  if ((b.num_records + 191) / 192 > 0x7fffffffu) return 1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  BatchDesc bo = b;  // with the processing order of a ragged batch
-  uint32_t *order = nullptr;
-  if (wants_length_order(b)) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
-                       s) != hipSuccess)
-      return 2;
-    const int orc = build_length_order(b.lengths, b.num_records, order, order + b.num_records, s);
-    if (orc) {
-      hipFreeAsync(order, s);
-      return orc;
-    }
-    bo.order = order;
-  }
-  if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->start), s);
-  open ? launch_mode<true>(keys, bo, sha1, nr, s) : launch_mode<false>(keys, bo, sha1, nr, s);
-  const int rc = (int)hipGetLastError();
-  if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  if (order) hipFreeAsync(order, s);
-  return rc;
+  const bool keyset = b.key_index != nullptr;
+  // (AES-256 comes with SHA-1 only.)
+  return launch_lane_kernel(
+      b, nr == 10 || (nr == 14 && sha1), tls_cbc_threads(open, nr, keyset), /*half_rule=*/true,
+      stream, ev, [&](const BatchDesc &bo, unsigned grid, unsigned threads, hipStream_t s) {
+        with_nr_keyset(nr, keyset, [&](auto NR, auto KEYSET) {
+          auto go = [&](auto OPEN, auto SHA1) {
+            if constexpr (NR.value == 10 || SHA1.value)
+              hipLaunchKernelGGL((tls_cbc_kernel<OPEN.value, NR.value, SHA1.value, KEYSET.value>),
+                                 dim3(grid), dim3(threads), 0, s, keys, bo);
+          };
+          if (open)
+            sha1 ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+          else
+            sha1 ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
+        });
+      });
 }
 
 }  // namespace bssl_amd

@@ -502,6 +502,53 @@ def test_device_batch_uniform_4096x64(aead):
         assert back[i, :64 + tlen].tobytes() == plains[i], i
 
 
+def test_device_batch_262147_short_records():
+    """Enough records that the one-key launcher takes its full-size workgroups
+    (768 lanes for every CU: from 196,608 records on 256 CUs; smaller batches
+    take half-size ones), with the AEAD whose seal and open one-key kernels
+    both have 768: 262,147 records of 16 bytes sealed into their 36-byte tag
+    slots.  A fixed-seed sample of 512 records, the first and the last are
+    compared with the restatement; all must seal with status 1, and the 48-byte
+    wire fragments open back: every plaintext, every out_lengths entry."""
+    aead, n, ln = "aes-256-cbc-sha1-tls", 262147, 16
+    slot, tlen = ref.overhead(aead), ref.tag_len(aead, ln)
+    assert (slot, tlen) == (36, 32)
+    rng = np.random.default_rng(262147)
+    key = ref.derive("many/" + aead, ref.key_len(aead))
+    src = rng.integers(0, 256, size=(n, ln), dtype=np.uint8)
+    nonces = rng.integers(0, 256, size=n * 16, dtype=np.uint8)
+    ads = rng.integers(0, 256, size=n * 11, dtype=np.uint8)
+    d_nonces, d_ads = _t(nonces), _t(ads)
+    d_out = torch.full((n * ln,), FILL, dtype=torch.uint8, device="cuda:0")
+    d_tags = torch.full((n * slot,), FILL, dtype=torch.uint8, device="cuda:0")
+    d_status = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    b = ba.make_batch(n, _t(src.reshape(-1)), d_out, d_tags, d_nonces, 16, d_ads, record_stride=ln,
+                      record_len=ln, ad_stride=11, ad_len=11, status=d_status)
+    sealer(aead, key).seal_batch_device(b)
+    torch.cuda.synchronize()
+    out, tags = d_out.cpu().numpy().reshape(n, ln), d_tags.cpu().numpy().reshape(n, slot)
+    assert bool((d_status == 1).all())
+    sample = set(np.random.default_rng(1).choice(n, size=512, replace=False).tolist()) | {0, n - 1}
+    for i in sorted(sample):
+        want = ref.seal(aead, key, nonces[i * 16:(i + 1) * 16].tobytes(), src[i].tobytes(),
+                        ads[i * 11:(i + 1) * 11].tobytes())
+        assert len(want) == ln + tlen
+        assert out[i].tobytes() == want[:ln], i
+        assert tags[i].tobytes() == want[ln:] + bytes(slot - tlen), i
+    # the wire fragments, opened in place
+    d_w = _t(np.concatenate([out, tags[:, :tlen]], axis=1).reshape(-1))
+    d_ol = torch.zeros(n, dtype=torch.int64, device="cuda:0")
+    d_status.zero_()
+    b2 = ba.make_batch(n, d_w, d_w, None, d_nonces, 16, d_ads, record_stride=ln + tlen,
+                       record_len=ln + tlen, ad_stride=11, ad_len=11, status=d_status,
+                       out_lengths=d_ol)
+    opener(aead, key).open_batch_device(b2)
+    torch.cuda.synchronize()
+    back = d_w.cpu().numpy().reshape(n, ln + tlen)
+    assert bool((d_status == 1).all()) and bool((d_ol == ln).all())
+    assert (back[:, :ln] == src).all()
+
+
 @pytest.mark.parametrize("aead", NAMES)
 def test_device_batch_ragged_8192_length_ordered(aead):
     """8192 records of 0..2048 bytes: a batch the launcher reorders by length

@@ -87,6 +87,11 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_TLS_AEAD_suffix_len", "BSSL_AMD_TLS_AEAD_sequence",
     "BSSL_AMD_TLS_AEAD_seal_records_device", "BSSL_AMD_TLS_AEAD_open_records_device",
     "BSSL_AMD_TLS_AEAD_new_cbc", "BSSL_AMD_test_tls_set_iv_key",
+    "BSSL_AMD_TLS_SET_new", "BSSL_AMD_TLS_SET_free", "BSSL_AMD_TLS_SET_num_connections",
+    "BSSL_AMD_TLS_SET_prefix_len", "BSSL_AMD_TLS_SET_suffix_len",
+    "BSSL_AMD_TLS_SET_set_connections", "BSSL_AMD_TLS_SET_clear_connections",
+    "BSSL_AMD_TLS_SET_sequences", "BSSL_AMD_TLS_SET_seal_records_device",
+    "BSSL_AMD_TLS_SET_open_records_device",
 ]
 TLS1_1_VERSION = 0x0302
 TLS1_2_VERSION = 0x0303
@@ -130,6 +135,13 @@ class BSSL_AMD_TLS_RECORDS(ctypes.Structure):
         ("type", ctypes.c_uint8), ("prefix", _P), ("suffix", _P), ("status", _P),
         # read for CBC contexts only (TlsAead.new_cbc)
         ("out_lengths", _P), ("explicit_ivs", _P),
+    ]
+
+
+class BSSL_AMD_TLS_SET_RECORDS(ctypes.Structure):
+    _fields_ = [
+        ("records", BSSL_AMD_TLS_RECORDS), ("num_runs", _S), ("run_connection", _P),
+        ("run_start", _P),
     ]
 
 
@@ -191,6 +203,18 @@ _SIGS = {
     "BSSL_AMD_TLS_AEAD_sequence": (ctypes.c_uint64, [_P]),
     "BSSL_AMD_TLS_AEAD_seal_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_RECORDS), _P]),
     "BSSL_AMD_TLS_AEAD_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_RECORDS), _P]),
+    "BSSL_AMD_TLS_SET_new": (_P, [_I, ctypes.c_uint16, _P, _S]),
+    "BSSL_AMD_TLS_SET_free": (None, [_P]),
+    "BSSL_AMD_TLS_SET_num_connections": (_S, [_P]),
+    "BSSL_AMD_TLS_SET_prefix_len": (_S, [_P]),
+    "BSSL_AMD_TLS_SET_suffix_len": (_S, [_P]),
+    "BSSL_AMD_TLS_SET_set_connections": (_I, [_P, _S, _S, _P, _P, _P, _P]),
+    "BSSL_AMD_TLS_SET_clear_connections": (_I, [_P, _S, _S, _P]),
+    "BSSL_AMD_TLS_SET_sequences": (_I, [_P, _S, _S, _P, _P]),
+    "BSSL_AMD_TLS_SET_seal_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
+                                                  _P]),
+    "BSSL_AMD_TLS_SET_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
+                                                  _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -470,6 +494,90 @@ def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, len
     r.prefix, r.suffix, r.status = _dptr(prefix), _dptr(suffix), _dptr(status)
     r.out_lengths, r.explicit_ivs = _dptr(out_lengths), _dptr(explicit_ivs)
     r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status, out_lengths, explicit_ivs)
+    return r
+
+
+class TlsSet:
+    """BSSL_AMD_TLS_SET: one direction of many connections of one cipher suite,
+    their keys, fixed IVs and sequence numbers resident on the device; one call
+    seals / opens a batch that mixes their records (include/bssl_amd/tls.h)."""
+
+    def __init__(self, direction, version, aead, num_connections):
+        if isinstance(aead, str):
+            aead = EVP_aead(aead)
+        self.h = _lib.BSSL_AMD_TLS_SET_new(direction, version, aead, num_connections)
+        if not self.h:
+            _fail("BSSL_AMD_TLS_SET_new")
+
+    @property
+    def num_connections(self):
+        return _lib.BSSL_AMD_TLS_SET_num_connections(self.h)
+
+    @property
+    def prefix_len(self):
+        return _lib.BSSL_AMD_TLS_SET_prefix_len(self.h)
+
+    @property
+    def suffix_len(self):
+        return _lib.BSSL_AMD_TLS_SET_suffix_len(self.h)
+
+    def set_connections(self, first, keys, fixed_ivs, seqs=None, stream=None):
+        """(Re)keys slots first.. from sequences of keys, fixed IVs and (or
+        None: all 0) starting sequence numbers."""
+        n = len(keys)
+        if len(fixed_ivs) != n or (seqs is not None and len(seqs) != n):
+            raise ValueError("keys, fixed_ivs and seqs differ in length")
+        kb = b"".join(bytes(k) for k in keys)
+        ib = b"".join(bytes(v) for v in fixed_ivs)
+        sb = None if seqs is None else (ctypes.c_uint64 * max(n, 1))(*seqs)
+        if not _lib.BSSL_AMD_TLS_SET_set_connections(self.h, first, n, kb, ib, sb,
+                                                     _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_set_connections")
+
+    def clear_connections(self, first, n, stream=None):
+        if not _lib.BSSL_AMD_TLS_SET_clear_connections(self.h, first, n, _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_clear_connections")
+
+    def sequences(self, first=0, n=None, stream=None):
+        """The next sequence numbers of slots first..first+n-1 (synchronises)."""
+        if n is None:
+            n = self.num_connections - first
+        out = (ctypes.c_uint64 * max(n, 1))()
+        if not _lib.BSSL_AMD_TLS_SET_sequences(self.h, first, n, out, _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_sequences")
+        return [out[i] for i in range(n)]
+
+    def seal_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_TLS_SET_seal_records_device(self.h, ctypes.byref(recs),
+                                                         _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_seal_records_device")
+
+    def open_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_TLS_SET_open_records_device(self.h, ctypes.byref(recs),
+                                                         _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_open_records_device")
+
+    def close(self):
+        if self.h:
+            _lib.BSSL_AMD_TLS_SET_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
+def make_tls_set_records(records, run_connection, run_start):
+    """BSSL_AMD_TLS_SET_RECORDS from a make_tls_records() structure and the
+    device tensors run_connection (int32 / uint32, num_runs entries) and
+    run_start (int64, num_runs + 1 entries); keeps references."""
+    r = BSSL_AMD_TLS_SET_RECORDS()
+    r.records = records
+    r.num_runs = 0 if run_connection is None else run_connection.numel()
+    r.run_connection, r.run_start = _dptr(run_connection), _dptr(run_start)
+    r._refs = (records, getattr(records, "_refs", None), run_connection, run_start)
     return r
 
 

@@ -2103,3 +2103,359 @@ int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_T
 }
 
 }  // extern "C"
+
+// ---- TLS connection sets (bssl_amd/tls.h, BSSL_AMD_TLS_SET) ---------------
+// One direction of many connections of one cipher suite: a keyset plus the
+// per-connection fixed IVs and sequence numbers on the device (TlsSetConn,
+// tls_set.hip), so that a mixed batch of records is one call that only
+// enqueues work.  The AEAD is the plain one (keysets have no per-key nonce
+// state): nothing but the set advances a connection's counter, so its nonces
+// increase by construction.
+
+struct bssl_amd_tls_set_st {
+  KeyMaterial *km;    // the keyset: num_connections keys, zero until installed
+  TlsSetConn *conns;  // device, num_connections entries
+  bool seal;
+  bool tls13;
+  bool xor_nonce;
+  uint32_t explicit_len;
+};
+
+namespace {
+
+// Whether slots first .. first + n - 1 are inside the set.
+bool set_range_ok(const BSSL_AMD_TLS_SET *s, size_t first, size_t n) {
+  if (s && first <= s->km->num_keys && n <= s->km->num_keys - first) return true;
+  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+  return false;
+}
+
+int tls_set_records(BSSL_AMD_TLS_SET *t, const BSSL_AMD_TLS_SET_RECORDS *sr, void *stream) {
+  const BSSL_AMD_TLS_RECORDS *r = sr ? &sr->records : nullptr;
+  if (!t || !r ||
+      (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix || sr->num_runs == 0 ||
+                          !sr->run_connection || !sr->run_start)) ||
+      sr->num_runs > 0xfffffffeu) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return 0;
+  }
+  const uint64_t n = r->num_records;
+  if (n == 0) return 1;
+  if (!t->seal && t->tls13 && !r->types) {  // open returns the inner types
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return 0;
+  }
+  const KeyMaterial *km = t->km;
+  if (!on_key_device(km)) return 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const uint32_t ad_stride = t->tls13 ? 5 : 13;
+  const uint32_t extra_len = t->tls13 ? 1 : 0;
+  const uint32_t tag_len = 16;
+  const uint32_t prefix_len = 5 + t->explicit_len;
+  const uint32_t suffix_len = extra_len + tag_len;
+  // Scratch per record: the key index, the nonce (12 B), the AD, the inner
+  // type (seal, TLS 1.3) and the flag.
+  uint8_t *buf = nullptr;
+  const size_t bytes = n * (4 + 12 + ad_stride + 1 + 1);
+  if (hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, s) != hipSuccess) {
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return 0;
+  }
+  uint32_t *d_key = reinterpret_cast<uint32_t *>(buf);
+  uint8_t *d_nonce = buf + 4 * n, *d_ad = d_nonce + 12 * n, *d_type = d_ad + ad_stride * n,
+          *d_valid = d_type + n;
+  TlsSetPrepare p;
+  memset(&p, 0, sizeof(p));
+  p.rec.n = n;
+  p.rec.lengths = r->lengths;
+  p.rec.record_len = r->record_len;
+  p.rec.types = r->types;
+  p.rec.type = r->type;
+  p.rec.xor_nonce = t->xor_nonce;
+  p.rec.tls13 = t->tls13;
+  p.rec.record_version = 0x0303;  // tls_record_version: TLS 1.3 records say TLS 1.2
+  p.rec.explicit_len = t->explicit_len;
+  p.rec.extra_len = extra_len;
+  p.rec.tag_len = tag_len;
+  p.rec.prefix_len = prefix_len;
+  p.rec.ad_stride = ad_stride;
+  p.rec.open = !t->seal;
+  p.rec.nonces = d_nonce;
+  p.rec.prefix = r->prefix;
+  p.rec.ad = d_ad;
+  p.rec.extra = d_type;
+  p.rec.valid = d_valid;
+  p.conns = t->conns;
+  p.num_connections = (uint32_t)km->num_keys;
+  p.num_runs = sr->num_runs;
+  p.run_connection = sr->run_connection;
+  p.run_start = sr->run_start;
+  p.key_index = d_key;
+  int ok = launch_tls_set_prepare(p, stream) == 0;
+  if (ok) {
+    BatchDesc d;
+    memset(&d, 0, sizeof(d));
+    d.in = r->in;
+    d.out = r->out;
+    d.offsets = r->offsets;
+    d.lengths = r->lengths;
+    d.record_stride = r->record_stride;
+    d.record_len = r->record_len;
+    d.nonces = d_nonce;
+    d.nonce_len = 12;
+    d.ad = d_ad;
+    d.ad_stride = ad_stride;
+    d.ad_len = ad_stride;
+    d.tags = r->suffix + extra_len;
+    d.tag_stride = suffix_len;
+    d.status = r->status;
+    d.key_index = d_key;
+    d.num_records = n;
+    d.tag_len = tag_len;
+    d.num_keys = (uint32_t)km->num_keys;
+    d.valid = d_valid;
+    if (extra_len) {
+      d.extra_len = extra_len;
+      if (t->seal) {  // inner type in, its ciphertext to the suffix
+        d.extra = d_type;
+        d.extra_stride = 1;
+        d.extra_out = r->suffix;
+        d.extra_out_stride = suffix_len;
+      } else {        // sealed inner type from the suffix, plaintext type out
+        d.extra = r->suffix;
+        d.extra_stride = suffix_len;
+        d.extra_out = r->types;
+        d.extra_out_stride = 1;
+      }
+    }
+    const KernelEvents *ev = timing_pair();
+    const int eng = gcm_engine();  // read once per call
+    const int rc = km->aead->kind == kAeadAesGcm
+                       ? launch_gcm(static_cast<const GcmKeyDev *>(km->dev), d, !t->seal, km->nr,
+                                    stream, ev, eng)
+                       : launch_chacha(static_cast<const ChaChaKeyDev *>(km->dev), d, !t->seal,
+                                       false, stream, ev);
+    t_timing.last_name = km->aead->kind == kAeadAesGcm ? gcm_kernel_name(eng) : "chacha_poly_kernel";
+    ok = rc == 0;
+    // TLS 1.2 open reports the header type (tls_record.cc:197-235).
+    if (ok && !t->seal && !t->tls13 && r->types)
+      ok = hipMemcpy2DAsync(r->types, 1, r->prefix, prefix_len, 1, n, hipMemcpyDeviceToDevice,
+                            s) == hipSuccess;
+  }
+  hipFreeAsync(buf, s);
+  if (!ok) {
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return 0;
+  }
+  return 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+BSSL_AMD_TLS_SET *BSSL_AMD_TLS_SET_new(enum evp_aead_direction_t direction, uint16_t version,
+                                       const EVP_AEAD *aead, size_t num_connections) {
+  // The rules and codes of BSSL_AMD_TLS_AEAD_new, all before any GPU call.
+  if ((version != BSSL_AMD_TLS1_2_VERSION && version != BSSL_AMD_TLS1_3_VERSION) || !aead ||
+      num_connections == 0 || num_connections > 0xfffffffeu) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return nullptr;
+  }
+  if (aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc) {
+    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
+    return nullptr;
+  }
+  const bool tls13 = version == BSSL_AMD_TLS1_3_VERSION;
+  if (!tls_record_aead(aead, tls13)) {
+    PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
+    return nullptr;
+  }
+  const bool gcm = aead->kind == kAeadAesGcm;
+  int dev = 0;
+  BSSL_AMD_TLS_SET *t = new (std::nothrow) bssl_amd_tls_set_st;
+  KeyMaterial *km =
+      t ? new (std::nothrow) KeyMaterial{aead, 0, num_connections, 0, nullptr, 0} : nullptr;
+  if (!km || hipGetDevice(&dev) != hipSuccess) {
+    delete km;
+    delete t;
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return nullptr;
+  }
+  km->device = dev;
+  km->nr = gcm ? (int)aead->key_len / 4 + 6 : 0;
+  km->bytes = num_connections * (gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev));
+  t->km = km;
+  t->conns = nullptr;
+  t->seal = direction == evp_aead_seal;
+  t->tls13 = tls13;
+  t->xor_nonce = tls13 || !gcm;
+  t->explicit_len = t->xor_nonce ? 0 : 8;
+  // All slots unset: zero keys, zero state.
+  const size_t conn_bytes = num_connections * sizeof(TlsSetConn);
+  bool ok = hipMalloc(&km->dev, km->bytes) == hipSuccess;
+  if (!ok) km->dev = nullptr;
+  ok = ok && hipMalloc(reinterpret_cast<void **>(&t->conns), conn_bytes) == hipSuccess;
+  ok = ok && hipMemset(km->dev, 0, km->bytes) == hipSuccess &&
+       hipMemset(t->conns, 0, conn_bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    if (t->conns) hipFree(t->conns);
+    if (km->dev) hipFree(km->dev);
+    delete km;
+    delete t;
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return nullptr;
+  }
+  return t;
+}
+
+void BSSL_AMD_TLS_SET_free(BSSL_AMD_TLS_SET *s) {
+  if (!s) return;
+  {
+    DeviceGuard g(s->km->device);
+    // As free_keys: drain the device, wipe, drain, free.
+    hipDeviceSynchronize();
+    hipMemset(s->conns, 0, s->km->num_keys * sizeof(TlsSetConn));
+    hipDeviceSynchronize();
+    hipFree(s->conns);
+  }
+  free_keys(s->km);
+  delete s;
+}
+
+size_t BSSL_AMD_TLS_SET_num_connections(const BSSL_AMD_TLS_SET *s) {
+  return s ? s->km->num_keys : 0;
+}
+
+size_t BSSL_AMD_TLS_SET_prefix_len(const BSSL_AMD_TLS_SET *s) { return 5 + s->explicit_len; }
+
+size_t BSSL_AMD_TLS_SET_suffix_len(const BSSL_AMD_TLS_SET *s) { return (s->tls13 ? 1 : 0) + 16; }
+
+int BSSL_AMD_TLS_SET_set_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
+                                     const uint8_t *keys, const uint8_t *fixed_ivs,
+                                     const uint64_t *seqs, void *hip_stream) {
+  if (!set_range_ok(s, first, n)) return 0;
+  if (n == 0) return 1;
+  if (!keys || !fixed_ivs) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return 0;
+  }
+  KeyMaterial *km = s->km;
+  if (!on_key_device(km)) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const size_t key_len = km->aead->key_len;
+  const size_t iv_len = s->xor_nonce ? 12 : 4;
+  const bool gcm = km->aead->kind == kAeadAesGcm;
+  // The expanded keys and the connection state staged in host memory, wiped
+  // on every path once the copies have read them.
+  std::vector<uint8_t> host_keys;
+  std::vector<TlsSetConn> host_conns(n);
+  struct Wipe {
+    std::vector<uint8_t> &k;
+    std::vector<TlsSetConn> &c;
+    ~Wipe() {
+      secure_zero(k.data(), k.size());
+      secure_zero(c.data(), c.size() * sizeof(TlsSetConn));
+    }
+  } wipe{host_keys, host_conns};
+  for (size_t i = 0; i < n; i++) {
+    TlsSetConn &c = host_conns[i];
+    memset(&c, 0, sizeof(c));
+    c.seq = seqs ? seqs[i] : 0;
+    uint8_t iv[12] = {0};
+    memcpy(iv, fixed_ivs + i * iv_len, iv_len);
+    for (int k = 0; k < 8; k++) c.iv_lo |= (uint64_t)iv[k] << (8 * k);
+    for (int k = 8; k < 12; k++) c.iv_hi |= (uint32_t)iv[k] << (8 * (k - 8));
+    secure_zero(iv, sizeof(iv));
+    c.live = 1;
+  }
+  bool ok = true;
+  if (gcm && n >= kDeviceKeySetupMin) {
+    // The device key setup writes the tables straight into the slots (and
+    // waits for the stream).
+    ok = gcm_key_setup_device(keys, key_len, n, static_cast<GcmKeyDev *>(km->dev) + first, st) == 0;
+  } else {
+    const size_t per = gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
+    host_keys.resize(n * per);
+    for (size_t i = 0; i < n && ok; i++) {
+      if (gcm)
+        ok = gcm_key_setup(keys + i * key_len, key_len,
+                           reinterpret_cast<GcmKeyDev *>(host_keys.data()) + i);
+      else
+        chacha_key_setup(keys + i * key_len, reinterpret_cast<ChaChaKeyDev *>(host_keys.data()) + i);
+    }
+    ok = ok && hipMemcpyAsync(static_cast<uint8_t *>(km->dev) + first * per, host_keys.data(),
+                              n * per, hipMemcpyHostToDevice, st) == hipSuccess;
+  }
+  ok = ok && hipMemcpyAsync(s->conns + first, host_conns.data(), n * sizeof(TlsSetConn),
+                            hipMemcpyHostToDevice, st) == hipSuccess;
+  // The copies read pageable host memory that is wiped on return: wait until
+  // they have.  (The host waits; the order on the stream is what the header
+  // promises either way.)
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  if (!ok) {
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return 0;
+  }
+  return 1;
+}
+
+int BSSL_AMD_TLS_SET_clear_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
+                                       void *hip_stream) {
+  if (!set_range_ok(s, first, n)) return 0;
+  if (n == 0) return 1;
+  KeyMaterial *km = s->km;
+  if (!on_key_device(km)) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const size_t per = km->aead->kind == kAeadAesGcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
+  if (hipMemsetAsync(static_cast<uint8_t *>(km->dev) + first * per, 0, n * per, st) != hipSuccess ||
+      hipMemsetAsync(s->conns + first, 0, n * sizeof(TlsSetConn), st) != hipSuccess) {
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return 0;
+  }
+  return 1;
+}
+
+int BSSL_AMD_TLS_SET_sequences(BSSL_AMD_TLS_SET *s, size_t first, size_t n, uint64_t *out,
+                               void *hip_stream) {
+  if (!set_range_ok(s, first, n)) return 0;
+  if (n == 0) return 1;
+  if (!out) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return 0;
+  }
+  if (!on_key_device(s->km)) return 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  // The entries as they are (they hold the IVs too: wiped afterwards).
+  std::vector<TlsSetConn> host(n);
+  const bool ok = hipMemcpyAsync(host.data(), s->conns + first, n * sizeof(TlsSetConn),
+                                 hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipStreamSynchronize(st) == hipSuccess;
+  for (size_t i = 0; i < n; i++) out[i] = ok ? host[i].seq : 0;
+  secure_zero(host.data(), n * sizeof(TlsSetConn));
+  if (!ok) {
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return 0;
+  }
+  return 1;
+}
+
+int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
+                                         void *hip_stream) {
+  if (s && !s->seal) {
+    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
+    return 0;
+  }
+  return tls_set_records(s, r, hip_stream);
+}
+
+int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
+                                         void *hip_stream) {
+  if (s && s->seal) {
+    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
+    return 0;
+  }
+  return tls_set_records(s, r, hip_stream);
+}
+
+}  // extern "C"

@@ -330,6 +330,38 @@ struct TlsPrepare {
   uint8_t *nonces, *prefix, *ad, *extra, *valid;
 };
 int launch_tls_prepare(const TlsPrepare &p, void *stream);
+// TLS connection sets (tls_set.hip; BSSL_AMD_TLS_SET): the per-connection
+// record-layer state on the device, one entry per slot.  All zero: unset.
+struct alignas(16) TlsSetConn {
+  uint64_t seq;     // the connection's next sequence number
+  // The fixed IV (TLS 1.2 AES-GCM: 4 bytes, then zeros): bytes 0..7 and
+  // 8..11, little-endian (TlsIv, tls_prepare.h).
+  uint64_t iv_lo;
+  uint32_t iv_hi;
+  uint32_t live;    // 1: keys and IV installed
+  // Within one call: ~j of the lowest non-empty run j that names this
+  // connection (atomicMax; 0: none).  0 between calls.
+  uint32_t claim;
+  uint32_t pad;
+};
+static_assert(sizeof(TlsSetConn) == 32, "layout");
+// A batch of records of many connections: records [run_start[j],
+// run_start[j+1]) belong to connection run_connection[j].  rec.fixed_iv and
+// rec.seq are unused (they come from conns[c]); rec.valid is written for every
+// record, and key_index[i] with its connection (0 for a record that has none).
+struct TlsSetPrepare {
+  TlsPrepare rec;
+  TlsSetConn *conns;
+  uint32_t num_connections;
+  uint64_t num_runs;
+  const uint32_t *run_connection;
+  const uint64_t *run_start;  // num_runs + 1 entries
+  uint32_t *key_index;
+};
+// Three launches in stream order: the runs claim their connections, every
+// record is prepared with its connection's next sequence number (or failed),
+// the runs that won advance their connections.  0 or a HIP error code.
+int launch_tls_set_prepare(const TlsSetPrepare &p, void *stream);
 // ... and of the TLS 1.1 / 1.2 AES-CBC-HMAC suites: the 16-byte CBC IV (seal:
 // the caller's, or bytes 0..15 of the ChaCha20 block of iv_key with counter
 // (uint32)seq and nonce words (uint32)(seq >> 32), 0, 0; open: the received

@@ -149,6 +149,113 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t,
                                                           const BSSL_AMD_TLS_RECORDS *r,
                                                           void *hip_stream);
 
+/* ---- Connection sets: one record batch across many connections ------------
+ *
+ * BSSL_AMD_TLS_SET is one direction of up to num_connections connections of
+ * ONE cipher suite.  Every slot holds what a BSSL_AMD_TLS_AEAD holds -- a key,
+ * a fixed IV and the next sequence number -- but on the device, so that one
+ * call protects a batch that mixes the records of many connections and only
+ * enqueues work.
+ *
+ * Records [run_start[j], run_start[j+1]) of a batch belong to connection
+ * c = run_connection[j] (per-connection send queues, concatenated).  Record i
+ * of run j gets the sequence number S[c] + (i - run_start[j]), where S[c] is
+ * the connection's next sequence number at the point of the stream where the
+ * call's work runs; afterwards S[c] has advanced by the run's record count.
+ * Prefix, body, suffix, status and returned type of every record are byte for
+ * byte what BSSL_AMD_TLS_AEAD_new(direction, version, aead, key_c, iv_c, S[c])
+ * produces for that connection's records in order.
+ *
+ * Seal and open only enqueue work on hip_stream: they never synchronise it,
+ * not for AES-GCM either.  The state of a set lives in stream order, so all
+ * calls of one set must be issued on one stream, or be ordered by the caller
+ * (events) as if they were.
+ *
+ * A record that fails has status 0 and the zeroed outputs the one-connection
+ * layer leaves; the other records of the batch are untouched.
+ *   - Seal: plaintext over 2^14 bytes; open: bad tag.  The record consumes
+ *     its sequence number, as in the one-connection layer.
+ *   - The record's sequence number would be 2^64 - 1, or past it
+ *     (tls_record.cc:302-306; e_aes.cc.inc:1087).  S[c] saturates at 2^64 - 1:
+ *     that record and all later ones of the connection fail.
+ *   - run_connection[j] is out of range, or the slot is unset.
+ *   - The connection already has an earlier non-empty run in this call: two
+ *     runs would both start from S[c].  The lowest j wins, the records of the
+ *     later runs fail and S[c] advances by the winning run only.
+ *   - The record index is not inside the run found for it (a malformed
+ *     run_start).  Nothing outside the batch's arrays is read or written.
+ * The records of the last four rules get no sequence number and consume none;
+ * on seal their prefix is zeroed too (there is no header to write).
+ *
+ * One deliberate departure from the reference: its tls13 AES-GCM AEAD learns
+ * its nonce mask from the first nonce and so only works for a context that
+ * starts at sequence number 0 (e_aes.cc.inc:1181-1194).  A set does not run
+ * the tls12 / tls13 nonce checks against host state: nothing but the set
+ * advances a connection's counter, so its nonces increase strictly by
+ * construction.  A slot may therefore be installed at any sequence number,
+ * TLS 1.3 AES-GCM included -- which is what moving a live connection onto the
+ * GPU needs.
+ *
+ * Out of scope: the CBC suites in a set; mixed suites in one set; TLS 1.3
+ * padded records on open (as in the one-connection layer); more than one run
+ * per connection per call. */
+typedef struct bssl_amd_tls_set_st BSSL_AMD_TLS_SET;
+
+/* The version / aead rules and codes of BSSL_AMD_TLS_AEAD_new (TLS 1.2 / 1.3;
+ * AES-128-GCM, AES-256-GCM, ChaCha20-Poly1305; the AES-CTR-HMAC and CBC AEADs
+ * CIPHER_R_CTRL_NOT_IMPLEMENTED); num_connections 0 or above 2^32 - 2 is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED.  All checks come before any GPU call.
+ * All slots start unset. */
+BSSL_AMD_EXPORT BSSL_AMD_TLS_SET *BSSL_AMD_TLS_SET_new(enum evp_aead_direction_t direction,
+                                                       uint16_t version, const EVP_AEAD *aead,
+                                                       size_t num_connections);
+/* Waits for the device, zeroes the key material on it and frees it. */
+BSSL_AMD_EXPORT void BSSL_AMD_TLS_SET_free(BSSL_AMD_TLS_SET *s);
+BSSL_AMD_EXPORT size_t BSSL_AMD_TLS_SET_num_connections(const BSSL_AMD_TLS_SET *s);
+BSSL_AMD_EXPORT size_t BSSL_AMD_TLS_SET_prefix_len(const BSSL_AMD_TLS_SET *s);
+BSSL_AMD_EXPORT size_t BSSL_AMD_TLS_SET_suffix_len(const BSSL_AMD_TLS_SET *s);
+
+/* (Re)key slots first .. first+n-1 from HOST arrays: n keys, n fixed IVs (4
+ * bytes each for TLS 1.2 AES-GCM, 12 otherwise), n starting sequence numbers
+ * (NULL: all 0).  Ordered on hip_stream with the set's batches: batches
+ * enqueued before it use the old keys, batches after it the new.  The host
+ * waits until the device has taken the staged key material (its host copies
+ * are zeroed before the call returns), and so for the work enqueued before it
+ * on hip_stream.  A slot range outside the set is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED. */
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_set_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
+                                                     const uint8_t *keys,
+                                                     const uint8_t *fixed_ivs,
+                                                     const uint64_t *seqs, void *hip_stream);
+/* Unset slots (key material zeroed on the device, in stream order); their
+ * records then fail.  Only enqueues work. */
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_clear_connections(BSSL_AMD_TLS_SET *s, size_t first,
+                                                       size_t n, void *hip_stream);
+/* Copies the next sequence numbers of slots first..first+n-1 to HOST memory
+ * (0 for an unset slot); synchronises hip_stream. */
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_sequences(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
+                                               uint64_t *out, void *hip_stream);
+
+typedef struct {
+  BSSL_AMD_TLS_RECORDS records; /* layout exactly as for one connection;
+                                   out_lengths / explicit_ivs are not read */
+  size_t num_runs;              /* at most 2^32 - 2 */
+  const uint32_t *run_connection; /* device, num_runs entries */
+  const uint64_t *run_start; /* device, num_runs + 1 entries, non-decreasing,
+                                run_start[0] = 0, run_start[num_runs] = num_records */
+} BSSL_AMD_TLS_SET_RECORDS;
+
+/* Seal (open) the batch; see above.  Returns 0 with nothing launched and an
+ * error queued for argument errors: NULL pointers as for one connection,
+ * num_runs == 0 with num_records != 0, missing run arrays, TLS 1.3 open
+ * without `types`, the wrong direction (CIPHER_R_INVALID_OPERATION). */
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s,
+                                                         const BSSL_AMD_TLS_SET_RECORDS *r,
+                                                         void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s,
+                                                         const BSSL_AMD_TLS_SET_RECORDS *r,
+                                                         void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,7 +90,9 @@ def ref_objects():
     return objs.split()
 
 
-def build_driver():
+def build_driver(name="ref_ccm_eax_gen"):
+    """Builds tests/golden/<name>.cc against the reference objects; returns the
+    program's path (make_golden_ctr_edge.py builds its generator the same way)."""
     objs = ref_objects()
     extra = []
     for rel in ("crypto/cipher/e_aeseax.cc", "crypto/aes/aes.cc"):
@@ -99,9 +101,9 @@ def build_driver():
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffunction-sections", "-fdata-sections",
                                f"-I{REF}/include", "-w", "-c", os.path.join(REF, rel), "-o", obj])
         extra.append(obj)
-    exe = os.path.join(OUT, "ref_ccm_eax_gen")
+    exe = os.path.join(OUT, name)
     subprocess.check_call(["g++", "-O2", "-std=c++17", f"-I{REF}/include",
-                           os.path.join(HERE, "ref_ccm_eax_gen.cc")] + extra + objs +
+                           os.path.join(HERE, name + ".cc")] + extra + objs +
                           ["-o", exe, "-lpthread", "-Wl,--gc-sections", "-static-libstdc++"])
     return exe
 

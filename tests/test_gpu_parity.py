@@ -757,6 +757,81 @@ def _split(rng, data, max_parts):
     return parts
 
 
+class IovArena:
+    """Records as chunks of one device input arena: chunks[c] = (offset,
+    bytes, in_place), record i owns chunks[starts[i]:starts[i + 1]]; outputs go
+    to the same offsets of an output arena, or in place; AD chunks
+    (offset, bytes) likewise."""
+
+    def __init__(self, chunks, starts, ad_chunks, ad_starts, nonces):
+        self.chunks, self.starts, self.n = chunks, starts, len(starts) - 1
+        self.nl = len(nonces[0])
+        size = max([off + len(part) for off, part, _ in chunks] + [0]) + 16
+        src = np.zeros(size, dtype=np.uint8)
+        for off, part, _ in chunks:
+            src[off:off + len(part)] = np.frombuffer(part, dtype=np.uint8)
+        adbuf = np.zeros(max([off + len(part) for off, part in ad_chunks] + [0]) + 16,
+                         dtype=np.uint8)
+        for off, part in ad_chunks:
+            adbuf[off:off + len(part)] = np.frombuffer(part, dtype=np.uint8)
+        self.d_src, self.d_ad = _t(src), _t(adbuf)
+        self.d_dst = torch.zeros_like(self.d_src)
+        ab = self.d_ad.data_ptr()
+        aiv = np.array([(ab + off, len(part)) for off, part in ad_chunks],
+                       dtype=np.int64).reshape(-1, 2)
+        self.d_aiv = _t(aiv)
+        self.d_starts = _t(np.array(starts, np.int64))
+        self.d_astarts = _t(np.array(ad_starts, np.int64))
+        self.d_nonce = _t(np.frombuffer(b"".join(nonces), dtype=np.uint8).copy())
+
+    def _gather(self, i, in_place_arena, other_arena):
+        parts = []
+        for off, part, in_place in self.chunks[self.starts[i]:self.starts[i + 1]]:
+            parts.append((in_place_arena if in_place else other_arena)[off:off + len(part)].tobytes())
+        return b"".join(parts)
+
+    def seal(self, ctx):
+        """Returns (ciphertexts, tags array, status array)."""
+        sb, db = self.d_src.data_ptr(), self.d_dst.data_ptr()
+        iov = np.array([(sb + off if ip else db + off, sb + off, len(part))
+                        for off, part, ip in self.chunks], dtype=np.int64).reshape(-1, 3)
+        d_tags = torch.zeros(16 * self.n, dtype=torch.uint8, device=DEV)
+        d_st = torch.full((self.n,), 7, dtype=torch.uint8, device=DEV)
+        b = ba.make_iov_batch(self.n, _t(iov), self.d_starts, d_tags, self.d_nonce, self.nl,
+                              aadvecs=self.d_aiv, aadvec_start=self.d_astarts, status=d_st)
+        ctx.sealv_batch_device(b)
+        torch.cuda.synchronize()
+        out_src, out_dst = self.d_src.cpu().numpy(), self.d_dst.cpu().numpy()
+        return ([self._gather(i, out_src, out_dst) for i in range(self.n)], d_tags.cpu().numpy(),
+                d_st.cpu().numpy())
+
+    def flip_ciphertext_bit(self, i, k, bit):
+        """Flips one bit of byte k of record i's ciphertext where the seal left it."""
+        for c in range(self.starts[i], self.starts[i + 1]):
+            off, part, ip = self.chunks[c]
+            if k < len(part):
+                (self.d_src if ip else self.d_dst)[off + k] ^= bit
+                return
+            k -= len(part)
+        raise IndexError(k)
+
+    def open(self, ctx, tags):
+        """Opens the ciphertext chunks (where the seal left them) into a third
+        arena.  Returns (outputs, status array)."""
+        sb, db = self.d_src.data_ptr(), self.d_dst.data_ptr()
+        d_back = torch.full_like(self.d_src, 0xAA)
+        kb = d_back.data_ptr()
+        iov2 = np.array([(kb + off, (sb if ip else db) + off, len(part))
+                         for off, part, ip in self.chunks], dtype=np.int64).reshape(-1, 3)
+        d_st = torch.full((self.n,), 7, dtype=torch.uint8, device=DEV)
+        b2 = ba.make_iov_batch(self.n, _t(iov2), self.d_starts, _t(tags), self.d_nonce, self.nl,
+                               aadvecs=self.d_aiv, aadvec_start=self.d_astarts, status=d_st)
+        ctx.openv_detached_batch_device(b2)
+        torch.cuda.synchronize()
+        back = d_back.cpu().numpy()
+        return [self._gather(i, back, back) for i in range(self.n)], d_st.cpu().numpy()
+
+
 @pytest.mark.parametrize("aead", ["aes-128-gcm", "aes-256-gcm", "chacha20-poly1305",
                                   "xchacha20-poly1305", "aes-128-gcm-siv", "aes-256-gcm-siv"])
 def test_iovec_batch_vs_oracle(aead):
@@ -785,64 +860,25 @@ def test_iovec_batch_vs_oracle(aead):
             ad_chunks.append((apos, part))
             apos += len(part)
         ad_starts.append(len(ad_chunks))
-    src = np.zeros(pos + 16, dtype=np.uint8)
-    for off, part, _ in chunks:
-        src[off:off + len(part)] = np.frombuffer(part, dtype=np.uint8)
-    adbuf = np.zeros(apos + 16, dtype=np.uint8)
-    for off, part in ad_chunks:
-        adbuf[off:off + len(part)] = np.frombuffer(part, dtype=np.uint8)
-    d_src, d_ad = _t(src), _t(adbuf)
-    d_dst = torch.zeros_like(d_src)
-    sb, db, ab = d_src.data_ptr(), d_dst.data_ptr(), d_ad.data_ptr()
-    iov = np.array([(sb + off if ip else db + off, sb + off, len(part)) for off, part, ip in chunks],
-                   dtype=np.int64).reshape(-1, 3)
-    aiv = np.array([(ab + off, len(part)) for off, part in ad_chunks], dtype=np.int64).reshape(-1, 2)
-    d_iov, d_aiv = _t(iov), _t(aiv)
-    d_starts, d_astarts = _t(np.array(starts, np.int64)), _t(np.array(ad_starts, np.int64))
-    d_nonce = _t(np.frombuffer(b"".join(nonces), dtype=np.uint8).copy())
-    d_tags = torch.zeros(16 * n, dtype=torch.uint8, device=DEV)
-    d_st = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+    arena = IovArena(chunks, starts, ad_chunks, ad_starts, nonces)
     ctx = ba.AEADCtx(aead, key, 16)
-    b = ba.make_iov_batch(n, d_iov, d_starts, d_tags, d_nonce, nl, aadvecs=d_aiv,
-                          aadvec_start=d_astarts, status=d_st)
-    ctx.sealv_batch_device(b)
-    torch.cuda.synchronize()
-    assert d_st.cpu().tolist() == [1] * n
-    out_src, out_dst, tags = d_src.cpu().numpy(), d_dst.cpu().numpy(), d_tags.cpu().numpy()
-
-    def gather(i, a, b_):
-        return b"".join((a if chunks[c][2] else b_)[chunks[c][0]:chunks[c][0] + len(chunks[c][1])]
-                        .tobytes() for c in range(starts[i], starts[i + 1]))
-
-    cts = []
+    cts, tags, st = arena.seal(ctx)
+    assert st.tolist() == [1] * n
     for i in range(n):
         ok, ct, tag = o.seal(ORACLE_ID[aead], key, nonces[i], pts[i], ads[i])
-        got = gather(i, out_src, out_dst)
-        assert ok and got == ct and tags[16 * i:16 * i + 16].tobytes() == tag, (i, len(pts[i]))
-        cts.append(ct)
+        assert ok and cts[i] == ct and tags[16 * i:16 * i + 16].tobytes() == tag, (i, len(pts[i]))
     # Open the ciphertext chunks (where the seal left them) into a third arena;
     # corrupt every 7th tag: those records fail and their chunks are zeroed.
-    d_back = torch.full_like(d_src, 0xAA)
-    kb = d_back.data_ptr()
-    iov2 = np.array([(kb + off, (sb if ip else db) + off, len(part)) for off, part, ip in chunks],
-                    dtype=np.int64).reshape(-1, 3)
     bad = set(range(0, n, 7))
     tg = tags.copy()
     for i in bad:
         tg[16 * i] ^= 1
-    d_st.fill_(7)
-    b2 = ba.make_iov_batch(n, _t(iov2), d_starts, _t(tg), d_nonce, nl, aadvecs=d_aiv,
-                           aadvec_start=d_astarts, status=d_st)
-    ctx.openv_detached_batch_device(b2)
-    torch.cuda.synchronize()
-    st, back = d_st.cpu().numpy(), d_back.cpu().numpy()
+    back, st = arena.open(ctx, tg)
     for i in range(n):
-        got = b"".join(back[chunks[c][0]:chunks[c][0] + len(chunks[c][1])].tobytes()
-                       for c in range(starts[i], starts[i + 1]))
         if i in bad:
-            assert st[i] == 0 and got == bytes(len(pts[i])), i
+            assert st[i] == 0 and back[i] == bytes(len(pts[i])), i
         else:
-            assert st[i] == 1 and got == pts[i], i
+            assert st[i] == 1 and back[i] == pts[i], i
 
 
 @pytest.mark.parametrize("aead", ["aes-128-gcm", "aes-256-gcm", "chacha20-poly1305",

@@ -6,21 +6,21 @@
 // (e_aes.cc.inc:733-924, 1040-1230; e_chacha20poly1305.cc:45-400) and the
 // CIPHER_R_* error queue.  All record arithmetic runs in the HIP kernels
 // (gcm.hip, chacha.hip): single-record calls upload their host buffers, run a
-// one-record batch and download the result.
+// one-record batch and download the result.  The error queue, the AEAD method
+// objects, key material, the EVP_AEAD_CTX_* surface, the batch and keyset
+// extensions and the timing hooks are here; the TLS record layer is
+// tls_api.cc, which uses what api_internal.h declares.
 #include <hip/hip_runtime.h>
-#include <errno.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/random.h>
 
 #include <new>
 #include <type_traits>
 #include <vector>
 
 #include "bssl_amd/aead.h"
-#include "bssl_amd/tls.h"
 #include "bssl_amd/test_hooks.h"
-#include "internal.h"
+#include "api_internal.h"
 
 using namespace bssl_amd;
 
@@ -31,15 +31,13 @@ namespace {
 constexpr int kNumErrors = 16;
 thread_local uint32_t t_err[kNumErrors];
 thread_local int t_err_top = 0, t_err_bottom = 0;
+}  // namespace
 
-void put_error(int reason) {
+void bssl_amd::put_error(int reason) {
   t_err_top = (t_err_top + 1) % kNumErrors;
   if (t_err_top == t_err_bottom) t_err_bottom = (t_err_bottom + 1) % kNumErrors;
   t_err[t_err_top] = ((uint32_t)(ERR_LIB_CIPHER & 0xff) << 24) | ((uint32_t)reason & 0xfff);
 }
-}  // namespace
-
-#define PUT_ERROR(reason) put_error(reason)
 
 extern "C" uint32_t ERR_get_error(void) {
   if (t_err_top == t_err_bottom) return 0;
@@ -65,18 +63,7 @@ extern "C" void ERR_clear_error(void) {
 }
 
 // ---------------------------------------------------------------------------
-// AEAD method objects (the reference's struct evp_aead_st vtable,
-// crypto/fipsmodule/cipher/internal.h:40-78, reduced to the parameters the
-// GPU path needs).
-struct evp_aead_st {
-  uint8_t key_len;
-  uint8_t nonce_len;
-  uint8_t overhead;
-  uint8_t max_tag_len;
-  AeadKind kind;
-  int tls;  // 0, 12 or 13: the tls12 / tls13 monotonic-nonce variants
-};
-
+// AEAD method objects (struct evp_aead_st, api_internal.h).
 namespace {
 const evp_aead_st kAes128Gcm = {16, 12, 16, 16, kAeadAesGcm, 0};
 const evp_aead_st kAes192Gcm = {24, 12, 16, 16, kAeadAesGcm, 0};
@@ -105,58 +92,6 @@ const evp_aead_st kAes256GcmTls12 = {32, 12, 16, 16, kAeadAesGcm, 12};
 const evp_aead_st kAes128GcmTls13 = {16, 12, 16, 16, kAeadAesGcm, 13};
 const evp_aead_st kAes256GcmTls13 = {32, 12, 16, 16, kAeadAesGcm, 13};
 
-// Device-resident key material for one or more keys.
-struct KeyMaterial {
-  const EVP_AEAD *aead;
-  int device;  // the HIP device the key material lives on
-  size_t num_keys;
-  int nr;
-  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], AesHmacKeyDev[num_keys] or
-  // ChaChaKeyDev[num_keys]
-  void *dev;
-  size_t bytes;
-  // kAeadTlsCbc: the one direction the keys work in (e_tls.cc:125-129, 274-278).
-  bool open_only = false;
-};
-
-// Makes `dev` the calling thread's current HIP device for the guard's scope
-// and restores the previous one (host-buffer calls may come from any thread,
-// as the reference's EVP_AEAD_CTX allows, aead.h:298-299).
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) return;
-    ok = prev == dev || hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (ok) hipSetDevice(prev);
-  }
-};
-
-// Device-batch calls take device pointers and a stream of the caller's
-// current device; they must be made on the device that holds the keys.
-bool on_key_device(const KeyMaterial *km) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != km->device) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return false;
-  }
-  return true;
-}
-
-// State kept in EVP_AEAD_CTX.state (560 bytes, reference aead.h:222-235).
-struct CtxState {
-  KeyMaterial *km;
-  uint64_t min_next_nonce;  // tls12/tls13 (e_aes.cc.inc:1041-1044, 1130-1134)
-  uint64_t mask;
-};
-static_assert(sizeof(CtxState) <= sizeof(((EVP_AEAD_CTX *)nullptr)->state), "state");
-
-CtxState *state_of(const EVP_AEAD_CTX *ctx) {
-  return reinterpret_cast<CtxState *>(const_cast<uint8_t *>(ctx->state.opaque));
-}
-
 bool is_cbcmac(const EVP_AEAD *aead) {
   return aead->kind == kAeadAesCcm || aead->kind == kAeadAesEax;
 }
@@ -167,8 +102,7 @@ bool is_lane_per_record(const EVP_AEAD *aead) {
   return is_cbcmac(aead) || aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc;
 }
 
-// kAeadTlsCbc: the MAC size, and the tag of a record (e_tls.cc:105-116).
-size_t tls_cbc_mac_len(const EVP_AEAD *aead) { return aead->max_tag_len; }
+// kAeadTlsCbc: the tag of a record (e_tls.cc:105-116).
 size_t tls_cbc_tag_len(const EVP_AEAD *aead, size_t in_len) {
   const size_t mac_len = tls_cbc_mac_len(aead);
   return mac_len + 16 - ((in_len + mac_len) & 15);
@@ -276,22 +210,6 @@ KeyMaterial *make_keys(const EVP_AEAD *aead, const uint8_t *keys, size_t num_key
   return km;
 }
 
-void free_keys(KeyMaterial *km) {
-  if (!km) return;
-  if (km->dev) {
-    DeviceGuard g(km->device);
-    // Batches may still be reading the keys on any stream of the device,
-    // including non-blocking ones the null-stream memset does not order
-    // against (seal/open_batch_device are asynchronous to the host): drain the
-    // device first, then wipe the device copy (OPENSSL_cleanse) and free it.
-    hipDeviceSynchronize();
-    hipMemset(km->dev, 0, km->bytes);
-    hipDeviceSynchronize();
-    hipFree(km->dev);
-  }
-  delete km;
-}
-
 // Kernel timing: when enabled, every batch launch records a pair of HIP
 // events around its bulk kernel (no host synchronisation);
 // BSSL_AMD_collect_kernel_times() waits for them and reports the durations.
@@ -336,11 +254,46 @@ const char *gcm_kernel_name(int engine) {
                                           : "gcm_kernel";
 }
 
-// Launch the bulk kernels of the AEAD over a filled-in descriptor.  Returns 0
-// or a HIP error code.  `gcm_eng`: the AES-GCM engine the caller already read
-// for this batch (-1: read it here), so one batch never sees two engines.
-int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stream,
-                int gcm_eng = -1) {
+}  // namespace
+
+// What tls_api.cc shares with this file (api_internal.h).
+namespace bssl_amd {
+
+bool on_key_device(const KeyMaterial *km) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != km->device) {
+    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+    return false;
+  }
+  return true;
+}
+
+size_t tls_cbc_mac_len(const EVP_AEAD *aead) { return aead->max_tag_len; }
+
+uint64_t load_be64(const uint8_t *p) {
+  uint64_t v = 0;
+  for (int i = 0; i < 8; i++) v = (v << 8) | p[i];
+  return v;
+}
+
+void free_keys(KeyMaterial *km) {
+  if (!km) return;
+  if (km->dev) {
+    DeviceGuard g(km->device);
+    // Batches may still be reading the keys on any stream of the device,
+    // including non-blocking ones the null-stream memset does not order
+    // against (seal/open_batch_device are asynchronous to the host): drain the
+    // device first, then wipe the device copy (OPENSSL_cleanse) and free it.
+    hipDeviceSynchronize();
+    hipMemset(km->dev, 0, km->bytes);
+    hipDeviceSynchronize();
+    hipFree(km->dev);
+  }
+  delete km;
+}
+
+// The one place that picks the launcher and the kernel name of an AEAD.
+int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stream, int gcm_eng) {
   int rc;
   const KernelEvents *ev = timing_pair();
   if (km->aead->kind == kAeadAesGcm) {
@@ -368,6 +321,10 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
   }
   return rc;
 }
+
+}  // namespace bssl_amd
+
+namespace {
 
 // Launch a batch over device buffers.  Returns 1 on success.
 // `one`: the single-record extras of one_record (completion word, inline
@@ -752,12 +709,6 @@ std::vector<uint8_t> gather_ad(const CRYPTO_IVEC *v, size_t n, size_t total) {
   return buf;
 }
 
-uint64_t load_be64(const uint8_t *p) {
-  uint64_t v = 0;
-  for (int i = 0; i < 8; i++) v = (v << 8) | p[i];
-  return v;
-}
-
 // The stateful TLS nonce checks of aead_aes_gcm_tls12_sealv /
 // aead_aes_gcm_tls13_sealv (e_aes.cc.inc:1071-1100, 1162-1202).
 bool tls_nonce_check(const EVP_AEAD_CTX *ctx, const uint8_t *nonce, size_t nonce_len) {
@@ -789,6 +740,34 @@ bool tls_nonce_check(const EVP_AEAD_CTX *ctx, const uint8_t *nonce, size_t nonce
   }
   st->min_next_nonce = given + 1;
   return true;
+}
+
+// ... and over a batch of seal calls of a tls12/tls13 context: the records are
+// N sealv calls in order, each with the monotonic-nonce check (tls_scan.hip);
+// records that fail it fail like the reference call (zeroed output, status 0)
+// and leave the state unchanged.  Returns the per-record flags (device; the
+// caller frees them on `stream` after its launch), or null with the error
+// queued.
+uint8_t *tls_nonce_flags(const EVP_AEAD_CTX *ctx, const uint8_t *nonces, size_t nonce_len,
+                         size_t n, void *stream) {
+  if (nonce_len != 12) {  // e_aes.cc.inc:1077-1080, 1168-1171 (seal only)
+    PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
+    return nullptr;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  CtxState *st = state_of(ctx);
+  uint8_t *valid = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void **>(&valid), n, s) != hipSuccess) {
+    PUT_ERROR(ERR_R_MALLOC_FAILURE);
+    return nullptr;
+  }
+  if (tls_nonce_scan(nonces, n, ctx->aead->tls, &st->min_next_nonce, &st->mask, valid, 0,
+                     stream) != 0) {
+    hipFreeAsync(valid, s);
+    PUT_ERROR(ERR_R_INTERNAL_ERROR);
+    return nullptr;
+  }
+  return valid;
 }
 
 // Common per-AEAD record checks before any device work (sealv/openv paths).
@@ -1407,24 +1386,11 @@ int EVP_AEAD_CTX_seal_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_BATCH
   if (!on_key_device(st->km)) return 0;
   if (!ctx->aead->tls)
     return run_batch(st->km, ctx->tag_len, batch, false, false, hip_stream);
-  if (batch->nonce_len != 12) {  // e_aes.cc.inc:1077-1080, 1168-1171 (seal only)
-    PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
-    return 0;
-  }
-  // tls12/tls13: the records are N sealv calls in order, each with the
-  // monotonic-nonce check (tls_scan.hip); records that fail it fail like the
-  // reference call (zeroed output, status 0) and leave the state unchanged.
-  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-  uint8_t *valid = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&valid), batch->num_records, s) != hipSuccess) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return 0;
-  }
-  int ok = tls_nonce_scan(batch->nonces, batch->num_records, ctx->aead->tls,
-                          &st->min_next_nonce, &st->mask, valid, 0, hip_stream) == 0;
-  if (!ok) PUT_ERROR(ERR_R_INTERNAL_ERROR);
-  if (ok) ok = run_batch(st->km, ctx->tag_len, batch, false, false, hip_stream, valid);
-  hipFreeAsync(valid, s);
+  uint8_t *valid = tls_nonce_flags(ctx, batch->nonces, batch->nonce_len, batch->num_records,
+                                   hip_stream);
+  if (!valid) return 0;
+  const int ok = run_batch(st->km, ctx->tag_len, batch, false, false, hip_stream, valid);
+  hipFreeAsync(valid, reinterpret_cast<hipStream_t>(hip_stream));
   return ok;
 }
 
@@ -1510,20 +1476,8 @@ int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   uint8_t *valid = nullptr;
   if (ctx->aead->tls) {  // the monotonic-nonce check, as for contiguous batches
-    if (batch->nonce_len != 12) {
-      PUT_ERROR(CIPHER_R_UNSUPPORTED_NONCE_SIZE);
-      return 0;
-    }
-    if (hipMallocAsync(reinterpret_cast<void **>(&valid), batch->num_records, s) != hipSuccess) {
-      PUT_ERROR(ERR_R_MALLOC_FAILURE);
-      return 0;
-    }
-    if (tls_nonce_scan(batch->nonces, batch->num_records, ctx->aead->tls, &st->min_next_nonce,
-                       &st->mask, valid, 0, hip_stream) != 0) {
-      hipFreeAsync(valid, s);
-      PUT_ERROR(ERR_R_INTERNAL_ERROR);
-      return 0;
-    }
+    valid = tls_nonce_flags(ctx, batch->nonces, batch->nonce_len, batch->num_records, hip_stream);
+    if (!valid) return 0;
   }
   const int rc = iov_batch_run(iov_desc(batch),
                                KeyRunner(st->km, ctx->tag_len, false, hip_stream, valid),
@@ -1691,771 +1645,5 @@ size_t BSSL_AMD_gcm_key_tables(const uint8_t *keys, size_t key_len, size_t n, in
 
 double BSSL_AMD_last_kernel_ms(void) { return t_timing.last_ms; }
 const char *BSSL_AMD_last_kernel_name(void) { return t_timing.last_name; }
-
-}  // extern "C"
-
-// ---- TLS record layer over device batches (bssl_amd/tls.h) ---------------
-// SSLAEADContext (ssl/ssl_aead_ctx.cc) + do_seal_record / tls_open_record
-// (ssl/tls_record.cc) for a batch of records; the per-record nonce, header,
-// AD and inner type are built on the device (tls_records.hip) and the records
-// go through the same bulk kernels as any batch.
-
-struct bssl_amd_tls_aead_st {
-  EVP_AEAD_CTX ctx;
-  bool seal;
-  bool tls13;
-  bool xor_nonce;
-  uint32_t explicit_len;
-  uint8_t fixed_iv[12];
-  uint64_t seq;
-  // The CBC suites (BSSL_AMD_TLS_AEAD_new_cbc): the record version, and for a
-  // sealing context the key of the IV generator (tls_records.hip).
-  bool cbc;
-  uint16_t version;
-  uint8_t iv_key[32];
-};
-
-namespace {
-
-const EVP_AEAD *tls_record_aead(const EVP_AEAD *aead, bool tls13) {
-  // ssl_cipher_get_evp_aead (ssl/ssl_cipher.cc): the nonce-checking variants
-  // for AES-GCM in TLS 1.2 / 1.3.
-  if (aead == &kAes128Gcm) return tls13 ? &kAes128GcmTls13 : &kAes128GcmTls12;
-  if (aead == &kAes256Gcm) return tls13 ? &kAes256GcmTls13 : &kAes256GcmTls12;
-  if (aead == &kChaChaPoly) return aead;
-  return nullptr;
-}
-
-// The CBC suites: random_variable_nonce_ / omit_length_in_ad_ of
-// SSLAEADContext (ssl_aead_ctx.cc:109-113) and the limits of tls_open_record
-// (tls_record.cc:117-133, 204-209).
-int tls_cbc_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *stream) {
-  // Open takes whole fragments (no suffix) and must report the lengths.
-  if (!r || (r->num_records && (!r->in || !r->out || !r->prefix ||
-                                (t->seal ? !r->suffix : !r->out_lengths)))) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const uint64_t n = r->num_records;
-  if (n == 0) return 1;
-  if (t->seq > UINT64_MAX - n) {
-    PUT_ERROR(ERR_R_OVERFLOW);
-    return 0;
-  }
-  const EVP_AEAD_CTX *ctx = &t->ctx;
-  CtxState *st = state_of(ctx);
-  if (!on_key_device(st->km)) return 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t mac_len = (uint32_t)tls_cbc_mac_len(ctx->aead);
-  // Scratch: IVs (16 B), AD (11 B) and flags per record.
-  uint8_t *buf = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&buf), n * (16 + 11 + 1), s) != hipSuccess) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return 0;
-  }
-  uint8_t *d_iv = buf, *d_ad = d_iv + 16 * n, *d_valid = d_ad + 11 * n;
-  int ok = hipMemsetAsync(d_valid, 1, n, s) == hipSuccess;
-  TlsCbcPrepare p;
-  memset(&p, 0, sizeof(p));
-  p.n = n;
-  p.lengths = r->lengths;
-  p.record_len = r->record_len;
-  p.types = t->seal ? r->types : nullptr;
-  p.type = r->type;
-  p.record_version = t->version;
-  p.mac_len = mac_len;
-  p.seq = t->seq;
-  p.open = !t->seal;
-  p.explicit_ivs = t->seal ? r->explicit_ivs : nullptr;
-  if (t->seal) memcpy(p.iv_key, t->iv_key, sizeof(p.iv_key));  // (little-endian host)
-  p.nonces = d_iv;
-  p.prefix = r->prefix;
-  p.ad = d_ad;
-  p.valid = d_valid;
-  p.types_out = t->seal ? nullptr : r->types;
-  if (ok) ok = launch_tls_cbc_prepare(p, stream) == 0;
-  secure_zero(&p, sizeof(p));
-  if (ok) {
-    BatchDesc d;
-    memset(&d, 0, sizeof(d));
-    d.in = r->in;
-    d.out = r->out;
-    d.offsets = r->offsets;
-    d.lengths = r->lengths;
-    d.record_stride = r->record_stride;
-    d.record_len = r->record_len;
-    d.nonces = d_iv;
-    d.nonce_len = 16;
-    d.ad = d_ad;
-    d.ad_stride = 11;
-    d.ad_len = 11;
-    d.tags = r->suffix;
-    d.status = r->status;
-    d.num_records = n;
-    d.tag_len = ctx->aead->overhead;  // the slot: the MAC and the longest padding
-    d.num_keys = 1;
-    d.valid = d_valid;
-    if (!t->seal) {
-      d.out_lengths = r->out_lengths;
-      d.max_plain_len = kTlsMaxPlainLen;
-    }
-    const KernelEvents *ev = timing_pair();
-    ok = launch_tls_cbc(static_cast<const AesHmacKeyDev *>(st->km->dev), d, mac_len == 20, !t->seal,
-                        st->km->nr, stream, ev) == 0;
-    t_timing.last_name = "tls_cbc_kernel";
-  }
-  hipFreeAsync(buf, s);
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  t->seq += n;
-  return 1;
-}
-
-int tls_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *stream) {
-  if (t && t->cbc) return tls_cbc_records(t, r, stream);
-  if (!t || !r || (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix))) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const uint64_t n = r->num_records;
-  if (n == 0) return 1;
-  // tls_record.cc:305-308: the sequence number must not wrap.
-  if (t->seq > UINT64_MAX - n) {
-    PUT_ERROR(ERR_R_OVERFLOW);
-    return 0;
-  }
-  if (!t->seal && t->tls13 && !r->types) {  // open returns the inner types
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const EVP_AEAD_CTX *ctx = &t->ctx;
-  CtxState *st = state_of(ctx);
-  if (!on_key_device(st->km)) return 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t ad_stride = t->tls13 ? 5 : 13;
-  const uint32_t extra_len = t->tls13 ? 1 : 0;
-  const uint32_t tag_len = ctx->tag_len;
-  const uint32_t prefix_len = 5 + t->explicit_len;
-  const uint32_t suffix_len = extra_len + tag_len;
-  // Scratch: nonces (12 B), AD, inner types (seal, TLS 1.3) and flags per record.
-  uint8_t *buf = nullptr;
-  const size_t bytes = n * (12 + ad_stride + 1 + 1);
-  if (hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, s) != hipSuccess) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return 0;
-  }
-  uint8_t *d_nonce = buf, *d_ad = d_nonce + 12 * n, *d_type = d_ad + ad_stride * n,
-          *d_valid = d_type + n;
-  int ok = hipMemsetAsync(d_valid, 1, n, s) == hipSuccess;
-  TlsPrepare p;
-  p.n = n;
-  p.lengths = r->lengths;
-  p.record_len = r->record_len;
-  p.types = r->types;
-  p.type = r->type;
-  memcpy(p.fixed_iv, t->fixed_iv, 12);
-  p.seq = t->seq;
-  p.xor_nonce = t->xor_nonce;
-  p.tls13 = t->tls13;
-  p.record_version = 0x0303;  // tls_record_version: TLS 1.3 records say TLS 1.2
-  p.explicit_len = t->explicit_len;
-  p.extra_len = extra_len;
-  p.tag_len = tag_len;
-  p.prefix_len = prefix_len;
-  p.ad_stride = ad_stride;
-  p.open = !t->seal;
-  p.nonces = d_nonce;
-  p.prefix = r->prefix;
-  p.ad = d_ad;
-  p.extra = d_type;
-  p.valid = d_valid;
-  if (ok) ok = launch_tls_prepare(p, stream) == 0;
-  if (ok && t->seal && ctx->aead->tls)  // the AEAD's own nonce check (sealv)
-    ok = tls_nonce_scan(d_nonce, n, ctx->aead->tls, &st->min_next_nonce, &st->mask, d_valid, 1,
-                        stream) == 0;
-  if (ok) {
-    BatchDesc d;
-    memset(&d, 0, sizeof(d));
-    d.in = r->in;
-    d.out = r->out;
-    d.offsets = r->offsets;
-    d.lengths = r->lengths;
-    d.record_stride = r->record_stride;
-    d.record_len = r->record_len;
-    d.nonces = d_nonce;
-    d.nonce_len = 12;
-    d.ad = d_ad;
-    d.ad_stride = ad_stride;
-    d.ad_len = ad_stride;
-    d.tags = r->suffix + extra_len;
-    d.tag_stride = suffix_len;
-    d.status = r->status;
-    d.num_records = n;
-    d.tag_len = tag_len;
-    d.num_keys = 1;
-    d.valid = d_valid;
-    if (extra_len) {
-      d.extra_len = extra_len;
-      if (t->seal) {  // inner type in, its ciphertext to the suffix
-        d.extra = d_type;
-        d.extra_stride = 1;
-        d.extra_out = r->suffix;
-        d.extra_out_stride = suffix_len;
-      } else {        // sealed inner type from the suffix, plaintext type out
-        d.extra = r->suffix;
-        d.extra_stride = suffix_len;
-        d.extra_out = r->types;
-        d.extra_out_stride = 1;
-      }
-    }
-    const KernelEvents *ev = timing_pair();
-    const int eng = gcm_engine();
-    const int rc = ctx->aead->kind == kAeadAesGcm
-                       ? launch_gcm(static_cast<const GcmKeyDev *>(st->km->dev), d, !t->seal,
-                                    st->km->nr, stream, ev, eng)
-                       : launch_chacha(static_cast<const ChaChaKeyDev *>(st->km->dev), d,
-                                       !t->seal, false, stream, ev);
-    t_timing.last_name = ctx->aead->kind == kAeadAesGcm ? gcm_kernel_name(eng) : "chacha_poly_kernel";
-    ok = rc == 0;
-    // TLS 1.2 open reports the header type (tls_record.cc:197-235).
-    if (ok && !t->seal && !t->tls13 && r->types)
-      ok = hipMemcpy2DAsync(r->types, 1, r->prefix, prefix_len, 1, n, hipMemcpyDeviceToDevice,
-                            s) == hipSuccess;
-  }
-  hipFreeAsync(buf, s);
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  t->seq += n;
-  return 1;
-}
-
-}  // namespace
-
-extern "C" {
-
-BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new(enum evp_aead_direction_t direction, uint16_t version,
-                                         const EVP_AEAD *aead, const uint8_t *key,
-                                         size_t key_len, const uint8_t *fixed_iv,
-                                         size_t fixed_iv_len, uint64_t seq) {
-  // SSLAEADContext::Create (ssl_aead_ctx.cc:44-123), AEAD suites only.
-  if ((version != BSSL_AMD_TLS1_2_VERSION && version != BSSL_AMD_TLS1_3_VERSION) || !aead ||
-      !fixed_iv) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return nullptr;
-  }
-  const bool tls13 = version == BSSL_AMD_TLS1_3_VERSION;
-  if (aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc) {  // no record layer for them here (tls.h)
-    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
-    return nullptr;
-  }
-  const EVP_AEAD *rec_aead = tls_record_aead(aead, tls13);
-  if (!rec_aead) {
-    PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
-    return nullptr;
-  }
-  // TLS 1.3 and TLS 1.2 ChaCha20-Poly1305 XOR a 12-byte IV with the sequence
-  // number; TLS 1.2 AES-GCM prepends a 4-byte IV to an 8-byte explicit nonce.
-  const bool xor_nonce = tls13 || aead->kind == kAeadChaChaPoly;
-  if (fixed_iv_len != (xor_nonce ? 12u : 4u)) {
-    PUT_ERROR(CIPHER_R_INVALID_NONCE_SIZE);
-    return nullptr;
-  }
-  BSSL_AMD_TLS_AEAD *t = new (std::nothrow) bssl_amd_tls_aead_st;
-  if (!t) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
-  EVP_AEAD_CTX_zero(&t->ctx);
-  if (!EVP_AEAD_CTX_init_with_direction(&t->ctx, rec_aead, key, key_len,
-                                        EVP_AEAD_DEFAULT_TAG_LENGTH, direction)) {
-    delete t;
-    return nullptr;
-  }
-  t->seal = direction == evp_aead_seal;
-  t->tls13 = tls13;
-  t->xor_nonce = xor_nonce;
-  t->explicit_len = xor_nonce ? 0 : 8;
-  memset(t->fixed_iv, 0, sizeof(t->fixed_iv));
-  memcpy(t->fixed_iv, fixed_iv, fixed_iv_len);
-  t->seq = seq;
-  t->cbc = false;
-  t->version = 0x0303;
-  memset(t->iv_key, 0, sizeof(t->iv_key));
-  if (t->seal && tls13 && t->ctx.aead->tls == 13 && seq != 0) {
-    // The tls13 AEAD takes its nonce mask from the first sealed nonce, which
-    // it assumes is sequence number 0 (e_aes.cc.inc:1181-1185).  A writer
-    // that starts mid-stream gets the state the AEAD would have after
-    // sealing records 0 .. seq-1: mask = the IV's low 64 bits, next >= seq.
-    CtxState *st = state_of(&t->ctx);
-    st->mask = load_be64(t->fixed_iv + 4);
-    st->min_next_nonce = seq;
-  }
-  return t;
-}
-
-BSSL_AMD_TLS_AEAD *BSSL_AMD_TLS_AEAD_new_cbc(enum evp_aead_direction_t direction, uint16_t version,
-                                             const EVP_AEAD *aead, const uint8_t *enc_key,
-                                             size_t enc_key_len, const uint8_t *mac_key,
-                                             size_t mac_key_len, uint64_t seq) {
-  // SSLAEADContext::Create (ssl_aead_ctx.cc:95-114) for a CBC suite with an
-  // explicit IV: TLS 1.1 and 1.2, no fixed IV.
-  if ((version != BSSL_AMD_TLS1_1_VERSION && version != BSSL_AMD_TLS1_2_VERSION) || !aead ||
-      !enc_key || !mac_key) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return nullptr;
-  }
-  if (aead->kind != kAeadTlsCbc) {
-    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
-    return nullptr;
-  }
-  if (mac_key_len != tls_cbc_mac_len(aead) || mac_key_len + enc_key_len != aead->key_len) {
-    PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
-    return nullptr;
-  }
-  BSSL_AMD_TLS_AEAD *t = new (std::nothrow) bssl_amd_tls_aead_st;
-  if (!t) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
-  memset(t->iv_key, 0, sizeof(t->iv_key));
-  t->seal = direction == evp_aead_seal;
-  if (t->seal) {
-    // The IV generator's key (RAND_bytes per record in the reference,
-    // ssl_aead_ctx.cc:343-347).
-    size_t got = 0;
-    while (got < sizeof(t->iv_key)) {
-      const ssize_t k = getrandom(t->iv_key + got, sizeof(t->iv_key) - got, 0);
-      if (k < 0 && errno == EINTR) continue;
-      if (k <= 0) break;
-      got += (size_t)k;
-    }
-    if (got != sizeof(t->iv_key)) {
-      secure_zero(t->iv_key, sizeof(t->iv_key));
-      delete t;
-      PUT_ERROR(ERR_R_INTERNAL_ERROR);
-      return nullptr;
-    }
-  }
-  uint8_t merged[64];  // MAC key || AES key, at most 52 bytes
-  memcpy(merged, mac_key, mac_key_len);
-  memcpy(merged + mac_key_len, enc_key, enc_key_len);
-  EVP_AEAD_CTX_zero(&t->ctx);
-  const int ok = EVP_AEAD_CTX_init_with_direction(&t->ctx, aead, merged, mac_key_len + enc_key_len,
-                                                  EVP_AEAD_DEFAULT_TAG_LENGTH, direction);
-  secure_zero(merged, sizeof(merged));
-  if (!ok) {
-    secure_zero(t->iv_key, sizeof(t->iv_key));
-    delete t;
-    return nullptr;
-  }
-  t->tls13 = false;
-  t->xor_nonce = false;
-  t->explicit_len = 16;
-  memset(t->fixed_iv, 0, sizeof(t->fixed_iv));
-  t->seq = seq;
-  t->cbc = true;
-  t->version = version;
-  return t;
-}
-
-void BSSL_AMD_TLS_AEAD_free(BSSL_AMD_TLS_AEAD *t) {
-  if (!t) return;
-  EVP_AEAD_CTX_cleanup(&t->ctx);
-  secure_zero(t->iv_key, sizeof(t->iv_key));
-  delete t;
-}
-
-int BSSL_AMD_test_tls_set_iv_key(BSSL_AMD_TLS_AEAD *t, const uint8_t key[32]) {
-  if (!t || !t->cbc || !t->seal || !key) return 0;
-  memcpy(t->iv_key, key, sizeof(t->iv_key));
-  return 1;
-}
-
-size_t BSSL_AMD_TLS_AEAD_prefix_len(const BSSL_AMD_TLS_AEAD *t) { return 5 + t->explicit_len; }
-
-size_t BSSL_AMD_TLS_AEAD_suffix_len(const BSSL_AMD_TLS_AEAD *t) {
-  if (t->cbc) return t->ctx.aead->overhead;  // the tag slot: the MAC and the longest padding
-  return (t->tls13 ? 1 : 0) + t->ctx.tag_len;
-}
-
-uint64_t BSSL_AMD_TLS_AEAD_sequence(const BSSL_AMD_TLS_AEAD *t) { return t->seq; }
-
-int BSSL_AMD_TLS_AEAD_seal_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
-                                          void *hip_stream) {
-  if (t && !t->seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return 0;
-  }
-  return tls_records(t, r, hip_stream);
-}
-
-int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
-                                          void *hip_stream) {
-  if (t && t->seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return 0;
-  }
-  return tls_records(t, r, hip_stream);
-}
-
-}  // extern "C"
-
-// ---- TLS connection sets (bssl_amd/tls.h, BSSL_AMD_TLS_SET) ---------------
-// One direction of many connections of one cipher suite: a keyset plus the
-// per-connection fixed IVs and sequence numbers on the device (TlsSetConn,
-// tls_set.hip), so that a mixed batch of records is one call that only
-// enqueues work.  The AEAD is the plain one (keysets have no per-key nonce
-// state): nothing but the set advances a connection's counter, so its nonces
-// increase by construction.
-
-struct bssl_amd_tls_set_st {
-  KeyMaterial *km;    // the keyset: num_connections keys, zero until installed
-  TlsSetConn *conns;  // device, num_connections entries
-  bool seal;
-  bool tls13;
-  bool xor_nonce;
-  uint32_t explicit_len;
-};
-
-namespace {
-
-// Whether slots first .. first + n - 1 are inside the set.
-bool set_range_ok(const BSSL_AMD_TLS_SET *s, size_t first, size_t n) {
-  if (s && first <= s->km->num_keys && n <= s->km->num_keys - first) return true;
-  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-  return false;
-}
-
-int tls_set_records(BSSL_AMD_TLS_SET *t, const BSSL_AMD_TLS_SET_RECORDS *sr, void *stream) {
-  const BSSL_AMD_TLS_RECORDS *r = sr ? &sr->records : nullptr;
-  if (!t || !r ||
-      (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix || sr->num_runs == 0 ||
-                          !sr->run_connection || !sr->run_start)) ||
-      sr->num_runs > 0xfffffffeu) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const uint64_t n = r->num_records;
-  if (n == 0) return 1;
-  if (!t->seal && t->tls13 && !r->types) {  // open returns the inner types
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const KeyMaterial *km = t->km;
-  if (!on_key_device(km)) return 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const uint32_t ad_stride = t->tls13 ? 5 : 13;
-  const uint32_t extra_len = t->tls13 ? 1 : 0;
-  const uint32_t tag_len = 16;
-  const uint32_t prefix_len = 5 + t->explicit_len;
-  const uint32_t suffix_len = extra_len + tag_len;
-  // Scratch per record: the key index, the nonce (12 B), the AD, the inner
-  // type (seal, TLS 1.3) and the flag.
-  uint8_t *buf = nullptr;
-  const size_t bytes = n * (4 + 12 + ad_stride + 1 + 1);
-  if (hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, s) != hipSuccess) {
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return 0;
-  }
-  uint32_t *d_key = reinterpret_cast<uint32_t *>(buf);
-  uint8_t *d_nonce = buf + 4 * n, *d_ad = d_nonce + 12 * n, *d_type = d_ad + ad_stride * n,
-          *d_valid = d_type + n;
-  TlsSetPrepare p;
-  memset(&p, 0, sizeof(p));
-  p.rec.n = n;
-  p.rec.lengths = r->lengths;
-  p.rec.record_len = r->record_len;
-  p.rec.types = r->types;
-  p.rec.type = r->type;
-  p.rec.xor_nonce = t->xor_nonce;
-  p.rec.tls13 = t->tls13;
-  p.rec.record_version = 0x0303;  // tls_record_version: TLS 1.3 records say TLS 1.2
-  p.rec.explicit_len = t->explicit_len;
-  p.rec.extra_len = extra_len;
-  p.rec.tag_len = tag_len;
-  p.rec.prefix_len = prefix_len;
-  p.rec.ad_stride = ad_stride;
-  p.rec.open = !t->seal;
-  p.rec.nonces = d_nonce;
-  p.rec.prefix = r->prefix;
-  p.rec.ad = d_ad;
-  p.rec.extra = d_type;
-  p.rec.valid = d_valid;
-  p.conns = t->conns;
-  p.num_connections = (uint32_t)km->num_keys;
-  p.num_runs = sr->num_runs;
-  p.run_connection = sr->run_connection;
-  p.run_start = sr->run_start;
-  p.key_index = d_key;
-  int ok = launch_tls_set_prepare(p, stream) == 0;
-  if (ok) {
-    BatchDesc d;
-    memset(&d, 0, sizeof(d));
-    d.in = r->in;
-    d.out = r->out;
-    d.offsets = r->offsets;
-    d.lengths = r->lengths;
-    d.record_stride = r->record_stride;
-    d.record_len = r->record_len;
-    d.nonces = d_nonce;
-    d.nonce_len = 12;
-    d.ad = d_ad;
-    d.ad_stride = ad_stride;
-    d.ad_len = ad_stride;
-    d.tags = r->suffix + extra_len;
-    d.tag_stride = suffix_len;
-    d.status = r->status;
-    d.key_index = d_key;
-    d.num_records = n;
-    d.tag_len = tag_len;
-    d.num_keys = (uint32_t)km->num_keys;
-    d.valid = d_valid;
-    if (extra_len) {
-      d.extra_len = extra_len;
-      if (t->seal) {  // inner type in, its ciphertext to the suffix
-        d.extra = d_type;
-        d.extra_stride = 1;
-        d.extra_out = r->suffix;
-        d.extra_out_stride = suffix_len;
-      } else {        // sealed inner type from the suffix, plaintext type out
-        d.extra = r->suffix;
-        d.extra_stride = suffix_len;
-        d.extra_out = r->types;
-        d.extra_out_stride = 1;
-      }
-    }
-    const KernelEvents *ev = timing_pair();
-    const int eng = gcm_engine();  // read once per call
-    const int rc = km->aead->kind == kAeadAesGcm
-                       ? launch_gcm(static_cast<const GcmKeyDev *>(km->dev), d, !t->seal, km->nr,
-                                    stream, ev, eng)
-                       : launch_chacha(static_cast<const ChaChaKeyDev *>(km->dev), d, !t->seal,
-                                       false, stream, ev);
-    t_timing.last_name = km->aead->kind == kAeadAesGcm ? gcm_kernel_name(eng) : "chacha_poly_kernel";
-    ok = rc == 0;
-    // TLS 1.2 open reports the header type (tls_record.cc:197-235).
-    if (ok && !t->seal && !t->tls13 && r->types)
-      ok = hipMemcpy2DAsync(r->types, 1, r->prefix, prefix_len, 1, n, hipMemcpyDeviceToDevice,
-                            s) == hipSuccess;
-  }
-  hipFreeAsync(buf, s);
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
-}
-
-}  // namespace
-
-extern "C" {
-
-BSSL_AMD_TLS_SET *BSSL_AMD_TLS_SET_new(enum evp_aead_direction_t direction, uint16_t version,
-                                       const EVP_AEAD *aead, size_t num_connections) {
-  // The rules and codes of BSSL_AMD_TLS_AEAD_new, all before any GPU call.
-  if ((version != BSSL_AMD_TLS1_2_VERSION && version != BSSL_AMD_TLS1_3_VERSION) || !aead ||
-      num_connections == 0 || num_connections > 0xfffffffeu) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return nullptr;
-  }
-  if (aead->kind == kAeadAesCtrHmac || aead->kind == kAeadTlsCbc) {
-    PUT_ERROR(CIPHER_R_CTRL_NOT_IMPLEMENTED);
-    return nullptr;
-  }
-  const bool tls13 = version == BSSL_AMD_TLS1_3_VERSION;
-  if (!tls_record_aead(aead, tls13)) {
-    PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
-    return nullptr;
-  }
-  const bool gcm = aead->kind == kAeadAesGcm;
-  int dev = 0;
-  BSSL_AMD_TLS_SET *t = new (std::nothrow) bssl_amd_tls_set_st;
-  KeyMaterial *km =
-      t ? new (std::nothrow) KeyMaterial{aead, 0, num_connections, 0, nullptr, 0} : nullptr;
-  if (!km || hipGetDevice(&dev) != hipSuccess) {
-    delete km;
-    delete t;
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
-  km->device = dev;
-  km->nr = gcm ? (int)aead->key_len / 4 + 6 : 0;
-  km->bytes = num_connections * (gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev));
-  t->km = km;
-  t->conns = nullptr;
-  t->seal = direction == evp_aead_seal;
-  t->tls13 = tls13;
-  t->xor_nonce = tls13 || !gcm;
-  t->explicit_len = t->xor_nonce ? 0 : 8;
-  // All slots unset: zero keys, zero state.
-  const size_t conn_bytes = num_connections * sizeof(TlsSetConn);
-  bool ok = hipMalloc(&km->dev, km->bytes) == hipSuccess;
-  if (!ok) km->dev = nullptr;
-  ok = ok && hipMalloc(reinterpret_cast<void **>(&t->conns), conn_bytes) == hipSuccess;
-  ok = ok && hipMemset(km->dev, 0, km->bytes) == hipSuccess &&
-       hipMemset(t->conns, 0, conn_bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
-    if (t->conns) hipFree(t->conns);
-    if (km->dev) hipFree(km->dev);
-    delete km;
-    delete t;
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
-  return t;
-}
-
-void BSSL_AMD_TLS_SET_free(BSSL_AMD_TLS_SET *s) {
-  if (!s) return;
-  {
-    DeviceGuard g(s->km->device);
-    // As free_keys: drain the device, wipe, drain, free.
-    hipDeviceSynchronize();
-    hipMemset(s->conns, 0, s->km->num_keys * sizeof(TlsSetConn));
-    hipDeviceSynchronize();
-    hipFree(s->conns);
-  }
-  free_keys(s->km);
-  delete s;
-}
-
-size_t BSSL_AMD_TLS_SET_num_connections(const BSSL_AMD_TLS_SET *s) {
-  return s ? s->km->num_keys : 0;
-}
-
-size_t BSSL_AMD_TLS_SET_prefix_len(const BSSL_AMD_TLS_SET *s) { return 5 + s->explicit_len; }
-
-size_t BSSL_AMD_TLS_SET_suffix_len(const BSSL_AMD_TLS_SET *s) { return (s->tls13 ? 1 : 0) + 16; }
-
-int BSSL_AMD_TLS_SET_set_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
-                                     const uint8_t *keys, const uint8_t *fixed_ivs,
-                                     const uint64_t *seqs, void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
-  if (n == 0) return 1;
-  if (!keys || !fixed_ivs) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  KeyMaterial *km = s->km;
-  if (!on_key_device(km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t key_len = km->aead->key_len;
-  const size_t iv_len = s->xor_nonce ? 12 : 4;
-  const bool gcm = km->aead->kind == kAeadAesGcm;
-  // The expanded keys and the connection state staged in host memory, wiped
-  // on every path once the copies have read them.
-  std::vector<uint8_t> host_keys;
-  std::vector<TlsSetConn> host_conns(n);
-  struct Wipe {
-    std::vector<uint8_t> &k;
-    std::vector<TlsSetConn> &c;
-    ~Wipe() {
-      secure_zero(k.data(), k.size());
-      secure_zero(c.data(), c.size() * sizeof(TlsSetConn));
-    }
-  } wipe{host_keys, host_conns};
-  for (size_t i = 0; i < n; i++) {
-    TlsSetConn &c = host_conns[i];
-    memset(&c, 0, sizeof(c));
-    c.seq = seqs ? seqs[i] : 0;
-    uint8_t iv[12] = {0};
-    memcpy(iv, fixed_ivs + i * iv_len, iv_len);
-    for (int k = 0; k < 8; k++) c.iv_lo |= (uint64_t)iv[k] << (8 * k);
-    for (int k = 8; k < 12; k++) c.iv_hi |= (uint32_t)iv[k] << (8 * (k - 8));
-    secure_zero(iv, sizeof(iv));
-    c.live = 1;
-  }
-  bool ok = true;
-  if (gcm && n >= kDeviceKeySetupMin) {
-    // The device key setup writes the tables straight into the slots (and
-    // waits for the stream).
-    ok = gcm_key_setup_device(keys, key_len, n, static_cast<GcmKeyDev *>(km->dev) + first, st) == 0;
-  } else {
-    const size_t per = gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-    host_keys.resize(n * per);
-    for (size_t i = 0; i < n && ok; i++) {
-      if (gcm)
-        ok = gcm_key_setup(keys + i * key_len, key_len,
-                           reinterpret_cast<GcmKeyDev *>(host_keys.data()) + i);
-      else
-        chacha_key_setup(keys + i * key_len, reinterpret_cast<ChaChaKeyDev *>(host_keys.data()) + i);
-    }
-    ok = ok && hipMemcpyAsync(static_cast<uint8_t *>(km->dev) + first * per, host_keys.data(),
-                              n * per, hipMemcpyHostToDevice, st) == hipSuccess;
-  }
-  ok = ok && hipMemcpyAsync(s->conns + first, host_conns.data(), n * sizeof(TlsSetConn),
-                            hipMemcpyHostToDevice, st) == hipSuccess;
-  // The copies read pageable host memory that is wiped on return: wait until
-  // they have.  (The host waits; the order on the stream is what the header
-  // promises either way.)
-  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
-}
-
-int BSSL_AMD_TLS_SET_clear_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
-                                       void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
-  if (n == 0) return 1;
-  KeyMaterial *km = s->km;
-  if (!on_key_device(km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t per = km->aead->kind == kAeadAesGcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-  if (hipMemsetAsync(static_cast<uint8_t *>(km->dev) + first * per, 0, n * per, st) != hipSuccess ||
-      hipMemsetAsync(s->conns + first, 0, n * sizeof(TlsSetConn), st) != hipSuccess) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
-}
-
-int BSSL_AMD_TLS_SET_sequences(BSSL_AMD_TLS_SET *s, size_t first, size_t n, uint64_t *out,
-                               void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
-  if (n == 0) return 1;
-  if (!out) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  if (!on_key_device(s->km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  // The entries as they are (they hold the IVs too: wiped afterwards).
-  std::vector<TlsSetConn> host(n);
-  const bool ok = hipMemcpyAsync(host.data(), s->conns + first, n * sizeof(TlsSetConn),
-                                 hipMemcpyDeviceToHost, st) == hipSuccess &&
-                  hipStreamSynchronize(st) == hipSuccess;
-  for (size_t i = 0; i < n; i++) out[i] = ok ? host[i].seq : 0;
-  secure_zero(host.data(), n * sizeof(TlsSetConn));
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
-}
-
-int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
-                                         void *hip_stream) {
-  if (s && !s->seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return 0;
-  }
-  return tls_set_records(s, r, hip_stream);
-}
-
-int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
-                                         void *hip_stream) {
-  if (s && s->seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return 0;
-  }
-  return tls_set_records(s, r, hip_stream);
-}
 
 }  // extern "C"

@@ -1,0 +1,86 @@
+// api_internal.h -- what the host C-ABI sources share: aead_api.cc defines it,
+// tls_api.cc (the record layer of bssl_amd/tls.h) uses it.  Host only; the
+// kernels see internal.h alone.
+#ifndef BSSL_AMD_API_INTERNAL_H
+#define BSSL_AMD_API_INTERNAL_H
+
+#include "bssl_amd/aead.h"
+#include "internal.h"
+
+// AEAD method objects (the reference's struct evp_aead_st vtable,
+// crypto/fipsmodule/cipher/internal.h:40-78, reduced to the parameters the
+// GPU path needs).
+struct evp_aead_st {
+  uint8_t key_len;
+  uint8_t nonce_len;
+  uint8_t overhead;
+  uint8_t max_tag_len;
+  bssl_amd::AeadKind kind;
+  int tls;  // 0, 12 or 13: the tls12 / tls13 monotonic-nonce variants
+};
+
+namespace bssl_amd {
+
+// The thread's error queue (ERR_get_error), library ERR_LIB_CIPHER.
+void put_error(int reason);
+#define PUT_ERROR(reason) ::bssl_amd::put_error(reason)
+
+// Device-resident key material for one or more keys.
+struct KeyMaterial {
+  const EVP_AEAD *aead;
+  int device;  // the HIP device the key material lives on
+  size_t num_keys;
+  int nr;
+  // GcmKeyDev[num_keys], CbcKeyDev[num_keys], AesHmacKeyDev[num_keys] or
+  // ChaChaKeyDev[num_keys]
+  void *dev;
+  size_t bytes;
+  // kAeadTlsCbc: the one direction the keys work in (e_tls.cc:125-129, 274-278).
+  bool open_only = false;
+};
+
+// Makes `dev` the calling thread's current HIP device for the guard's scope
+// and restores the previous one (host-buffer calls may come from any thread,
+// as the reference's EVP_AEAD_CTX allows, aead.h:298-299).
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) return;
+    ok = prev == dev || hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceGuard() {
+    if (ok) hipSetDevice(prev);
+  }
+};
+
+// State kept in EVP_AEAD_CTX.state (560 bytes, reference aead.h:222-235).
+struct CtxState {
+  KeyMaterial *km;
+  uint64_t min_next_nonce;  // tls12/tls13 (e_aes.cc.inc:1041-1044, 1130-1134)
+  uint64_t mask;
+};
+static_assert(sizeof(CtxState) <= sizeof(((EVP_AEAD_CTX *)nullptr)->state), "state");
+
+inline CtxState *state_of(const EVP_AEAD_CTX *ctx) {
+  return reinterpret_cast<CtxState *>(const_cast<uint8_t *>(ctx->state.opaque));
+}
+
+// Device-batch calls take device pointers and a stream of the caller's
+// current device; they must be made on the device that holds the keys.
+bool on_key_device(const KeyMaterial *km);
+// Drains the device, wipes the device copy of the keys and frees it.
+void free_keys(KeyMaterial *km);
+// Launch the bulk kernels of the AEAD over a filled-in descriptor, with the
+// timing pair and the kernel name of BSSL_AMD_set_kernel_timing.  Returns 0 or
+// a HIP error code.  `gcm_eng`: the AES-GCM engine the caller already read for
+// this batch (-1: read it here), so one batch never sees two engines.
+int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stream,
+                int gcm_eng = -1);
+// kAeadTlsCbc: the MAC size (e_tls.cc:105-116).
+size_t tls_cbc_mac_len(const EVP_AEAD *aead);
+uint64_t load_be64(const uint8_t *p);
+
+}  // namespace bssl_amd
+
+#endif

@@ -727,6 +727,38 @@ def test_tls_record_layer(version, aead):
         assert st2[i] == 1 and b == records[i] and ot[i] == types[i], i
 
 
+@pytest.mark.parametrize("version,aead,engine,kernel",
+                         [(0x0304, "aes-128-gcm", "table", "gcm_kernel"),
+                          (0x0304, "aes-128-gcm", "bs", "gcm_bs_kernel"),
+                          (0x0303, "aes-128-gcm", "table", "gcm_kernel"),
+                          (0x0303, "chacha20-poly1305", None, "chacha_poly_kernel")])
+def test_tls_record_layer_kernel_identity(version, aead, engine, kernel, aes_engine):
+    """One record-layer call runs one bulk kernel, the AEAD's (the engine's),
+    and records one timing pair for it."""
+    if engine:
+        aes_engine(engine)
+    n, rlen = 70, 64
+    xor = version == 0x0304 or aead == "chacha20-poly1305"
+    sealer = ba.TlsAead(ba.evp_aead_seal, version, aead, bytes(range(16 if "128" in aead else 32)),
+                        bytes(12 if xor else 4))
+    d_in = torch.zeros(n * rlen, dtype=torch.uint8, device=DEV)
+    d_pre = torch.zeros(n * sealer.prefix_len, dtype=torch.uint8, device=DEV)
+    d_suf = torch.zeros(n * sealer.suffix_len, dtype=torch.uint8, device=DEV)
+    d_st = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    r = ba.make_tls_records(n, d_in, torch.zeros_like(d_in), d_pre, d_suf, record_stride=rlen,
+                            record_len=rlen, status=d_st)
+    ba.set_kernel_timing(True)
+    try:
+        ba.collect_kernel_times()  # (pairs an earlier test may have left)
+        sealer.seal_records_device(r)
+        times = ba.collect_kernel_times()
+    finally:
+        ba.set_kernel_timing(False)
+    assert len(times) == 1 and times[0] > 0
+    assert ba.last_kernel_name() == kernel
+    assert bool(d_st.all()) and sealer.sequence == n
+
+
 def test_tls_record_layer_errors():
     key, iv = bytes(16), bytes(12)
     with pytest.raises(ba.AEADError) as e:  # TLS 1.2 AES-GCM wants a 4-byte fixed IV

@@ -499,3 +499,40 @@ def test_open_fails_exactly_the_tampered_records(version, aead, engine, aes_engi
         # The records after a failed one still open: it consumed its number.
         assert st == 1 and pt == records[i] and ty == types[i], i
     assert opener.sequences() == sealer.sequences() == [conns[0][2] + 30, 7 + 20, (1 << 48) + 20]
+
+
+# ---------------------------------------------------------------------------
+# 8. The bulk kernel.
+
+@pytest.mark.parametrize("version,aead,engine,kernel",
+                         [(0x0304, "aes-128-gcm", "table", "gcm_kernel"),
+                          (0x0304, "aes-128-gcm", "bs", "gcm_bs_kernel"),
+                          (0x0303, "aes-128-gcm", "table", "gcm_kernel"),
+                          (0x0303, "chacha20-poly1305", None, "chacha_poly_kernel")])
+def test_kernel_identity(version, aead, engine, kernel, aes_engine):
+    """One call of a set runs one bulk kernel, the AEAD's (the engine's), and
+    records one timing pair for it."""
+    if engine:
+        aes_engine(engine)
+    rng = random.Random(version + len(aead))
+    ts = ba.TlsSet(ba.evp_aead_seal, version, aead, 4)
+    _install(ts, [_conn(rng, version, aead, s) for s in (0, 9, 0, 1 << 40)])
+    n, rlen = 70, 64
+    d_in = torch.zeros(n * rlen, dtype=torch.uint8, device=DEV)
+    d_pre = torch.zeros(n * ts.prefix_len, dtype=torch.uint8, device=DEV)
+    d_suf = torch.zeros(n * ts.suffix_len, dtype=torch.uint8, device=DEV)
+    d_st = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    recs = ba.make_tls_records(n, d_in, torch.zeros_like(d_in), d_pre, d_suf, record_stride=rlen,
+                               record_len=rlen, status=d_st)
+    sr = ba.make_tls_set_records(recs, _t(np.array([3, 1], dtype=np.int32)),
+                                 _t(np.array([0, 30, n], dtype=np.int64)))
+    ba.set_kernel_timing(True)
+    try:
+        ba.collect_kernel_times()  # (pairs an earlier test may have left)
+        ts.seal_records_device(sr)
+        times = ba.collect_kernel_times()
+    finally:
+        ba.set_kernel_timing(False)
+    assert len(times) == 1 and times[0] > 0
+    assert ba.last_kernel_name() == kernel
+    assert bool(d_st.all()) and ts.sequences() == [0, 49, 0, (1 << 40) + 30]

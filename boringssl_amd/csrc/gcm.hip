@@ -29,6 +29,7 @@
 //   key at a time; records are visited in tiles of 32 and a tile whose
 //   records use several keys is processed in one pass per distinct key.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -277,7 +278,15 @@ struct WindowCache {
   __device__ __forceinline__ void update(uint32_t ctr, uint32_t s3, uint32_t c0, uint32_t c1,
                                          uint32_t c2, const RoundKeys &rk,
                                          const uint8_t *smem, uint32_t lc0, uint32_t lc1) {
-    if ((ctr >> 8) == win) return;
+    if ((ctr >> 8) != win) refresh<T>(ctr, s3, c0, c1, c2, rk, smem, lc0, lc1);
+  }
+
+  // The window's constants (they depend on the counter's upper 24 bits only,
+  // so a lane already inside the window recomputes what it holds).
+  template <uint32_t T>
+  __device__ __forceinline__ void refresh(uint32_t ctr, uint32_t s3, uint32_t c0, uint32_t c1,
+                                          uint32_t c2, const RoundKeys &rk,
+                                          const uint8_t *smem, uint32_t lc0, uint32_t lc1) {
     win = ctr >> 8;
     k1 = round_col<T>(smem, lc0, lc1, c1, c2, s3, c0, rk.w[1][1]);
     k2 = round_col<T>(smem, lc0, lc1, c2, s3, c0, c1, rk.w[1][2]);
@@ -308,6 +317,16 @@ struct WindowCache {
 };
 
 #include "gcm_rounds.inc"
+
+// Minimum over the wave of a value that is uniform within each L-lane group
+// (group_max, gcm_common.h).
+template <int L>
+__device__ __forceinline__ int group_min(int v) {
+  int m = __builtin_amdgcn_readlane(v, 0);
+#pragma unroll
+  for (int k = 1; k < 64 / L; k++) m = min(m, __builtin_amdgcn_readlane(v, k * L));
+  return m;
+}
 
 // GHASH steps carried by middle round i (rounds 3..NR-1 -> i = 0..NR-4) of
 // the one-block-per-lane kernel: AES-128 has 7 such rounds (3,3,2,2,2,2,2),
@@ -476,6 +495,17 @@ __device__ __forceinline__ void iov_store_blk(uint8_t *p, uint4 y) {
   else
     store_blk_nt(p, y);
 }
+#ifndef GCM_STEADY
+#define GCM_STEADY 1  // (A/B: 0 = every step through the general loop)
+#endif
+// Plaintext buffers of the steady loop: its loads run GCM_STEADY_DEPTH - 1
+// steps ahead.  (A/B on config 2 against the general loop, DESIGN.md 5.2s:
+// 2 = +0.6 %; in one job 3 = +1.9 %, 4 = +1.4 %, 5 = +1.9 % -- at 4 and 5
+// hipcc rotates the buffers through copies and waits vmcnt(1) once per trip.)
+#ifndef GCM_STEADY_DEPTH
+#define GCM_STEADY_DEPTH 3
+#endif
+static_assert(GCM_STEADY_DEPTH >= 2, "one buffer in use, one in flight");
 #ifndef GCM_TL_TSTORE
 #define GCM_TL_TSTORE 0  // (A/B: temporal stores wherever the loads are temporal)
 #endif
@@ -605,6 +635,23 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
       return IovDescG{b.iovecs};
     }
   };
+  // Whole blocks of a contiguous record: one dwordx4 each way.
+  // (Loads: TL at L = 4 as the stores, config G 850-883 -> 888-904 GiB/s, same
+  // box, profiles/r06/s17.  Stores: temporal at L = 4, +2 % on config G's
+  // 64-byte runs, same box; non-temporal ones for the longer runs of L = 8 /
+  // 16, profiles/r05/r5s19.)
+  auto load_whole = [&](const uint8_t *p) {
+    if constexpr (TL || GCM_TLOAD_ALL)
+      return load16_any(p);
+    else
+      return load_blk_nt(p);
+  };
+  auto store_whole = [&](uint8_t *p, uint4 y) {
+    if constexpr (L == 4 || (TL && GCM_TL_TSTORE))
+      store_blk(p, y);
+    else
+      store_blk_nt(p, y);
+  };
   // (Left undefined when not loaded: such a block is never stored or hashed
   // from this value, and a zero-fill would be a VALU write that the waitcnt
   // pass orders after the previous store.)
@@ -646,14 +693,7 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
       }
       return v;
     }
-    if (j < nfull) {
-      // (TL at L = 4 as the stores below: config G 850-883 -> 888-904
-      // GiB/s, same box, profiles/r06/s17)
-      if constexpr (TL || GCM_TLOAD_ALL)
-        v = load16_any(src + (uint64_t)j * 16);
-      else
-        v = load_blk_nt(src + (uint64_t)j * 16);
-    }
+    if (j < nfull) v = load_whole(src + (uint64_t)j * 16);
     return v;
   };
   // One iteration: block j = it*16 + q, plaintext (if full) already in x,
@@ -668,7 +708,10 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
     wc.update<T>(ctr, s3, c0, c1, c2, rk, smem, lc0, lc1);
     wc.rounds12<T>(k0, s3, cur[0], cur[1], cur[2], cur[3], smem, lc0, lc1);
   }
-  auto step = [&](int it, uint4 x) {
+  // The rounds of block j = it*L + q: returns its keystream block and leaves
+  // acc * H^L in h.g.  `uniform` (the steady loop below): the window cache is
+  // refreshed by the whole wave when any lane needs it (a scalar branch).
+  auto rounds = [&](auto uniform, int it, Gh8 &h) {
     if constexpr (RP) {
       switch ((prio_base + it) & 3) {
         case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -680,14 +723,22 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
     const uint32_t j = (uint32_t)it * L + q;
     const uint32_t ctrn = ctr0 + 1u + (uint32_t)(j + L);  // next block, inc32 mod 2^32
     uint32_t xs = bswap32(ctrn) ^ rk.w[0][3];
-    wc.update<T>(ctrn, xs, c0, c1, c2, rk, smem, lc0, lc1);
-    Gh8 h;
+    if constexpr (decltype(uniform)::value) {
+      if (__ballot((ctrn >> 8) != wc.win)) wc.refresh<T>(ctrn, xs, c0, c1, c2, rk, smem, lc0, lc1);
+    } else {
+      wc.update<T>(ctrn, xs, c0, c1, c2, rk, smem, lc0, lc1);
+    }
     g8_rotate(h, acc, rs1, rs2, rbs);
     h.g = make_uint4(0, 0, 0, 0);
     uint32_t sa[4] = {cur[0], cur[1], cur[2], cur[3]};
     rounds_s1<0, NR>(sa, rk, lc0, lc1, h, P, xs, wc, k0, cur);
     asm_last_s1(sa, rk.w[NR], lc0);
-    const uint4 ks = make_uint4(sa[0], sa[1], sa[2], sa[3]);
+    return make_uint4(sa[0], sa[1], sa[2], sa[3]);
+  };
+  auto step = [&](int it, uint4 x) {
+    const uint32_t j = (uint32_t)it * L + q;
+    Gh8 h;
+    const uint4 ks = rounds(std::false_type{}, it, h);
     uint4 y = xor4(x, ks);
     if constexpr (IOV) {
       if (st_left >= 16) {
@@ -721,12 +772,7 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
       return;
     }
     if (j < nfull) {
-      // (L = 4: temporal stores, +2 % on config G's 64-byte runs, same box;
-      // non-temporal ones for the longer runs of L = 8 / 16, profiles/r05/r5s19)
-      if constexpr (L == 4 || (TL && GCM_TL_TSTORE))
-        store_blk(dst + (uint64_t)j * 16, y);
-      else
-        store_blk_nt(dst + (uint64_t)j * 16, y);
+      store_whole(dst + (uint64_t)j * 16, y);
     } else if (j < nb) {
       const uint32_t n = (uint32_t)umin64(m.len + m.xlen - (uint64_t)j * 16, 16);
       if constexpr (XT) {
@@ -752,6 +798,45 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
   else
     x0 = in.x0;
   int it = 0;
+  // Steady loop: while every live record of the wave has a whole block in
+  // every lane, the steps need no `j < nfull` / `j < nb` paths, so the body has
+  // no exec-mask branch: the load and the store are unconditional dwordx4 at
+  // running pointers, the window cache is refreshed behind a scalar branch, and
+  // the wait for a step's plaintext counts -- the loads and stores issued
+  // after that block's load stay in flight (vmcnt(4) with D = 3 buffers).
+  // Steps [0, nst) run here, D per trip, dead and inactive records masked once
+  // around the loop.  nst leaves the last D - 1 whole steps out, so every
+  // block loaded ahead is a whole block of the record, and the general loop
+  // below takes over with x0 (step nst's block), cur, wc and acc as it would
+  // have left them itself; it loads the other blocks that were in flight again.
+  if constexpr (!IOV && GCM_STEADY) {
+    const int whole = group_min<L>(live ? (int)(nfull / L) : INT_MAX);  // (nfull / L < 2^30)
+    constexpr int D = GCM_STEADY_DEPTH;  // plaintext buffers: loads run D - 1 steps ahead
+    const int nst = whole == INT_MAX ? 0 : max(whole - D + 1, 0) / D * D;  // (all dead: none)
+    if (nst > 0 && live) {
+      const uint8_t *lp = src + 16 * q + 16 * L;  // the block of step s + 1
+      uint8_t *sp = dst + 16 * q;                 // the block of step s
+      uint4 xb[D];
+      xb[0] = x0;
+#pragma unroll
+      for (int k = 1; k < D - 1; k++) xb[k] = load_whole(lp + (k - 1) * 16 * L);
+      for (int s = 0; s < nst; s += D) {
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+          xb[(k + D - 1) % D] = load_whole(lp + (k + D - 2) * 16 * L);  // step s + k + D - 1
+          Gh8 h;
+          const uint4 ks = rounds(std::true_type{}, s + k, h);
+          const uint4 y = xor4(xb[k], ks);
+          store_whole(sp + k * 16 * L, y);
+          acc = xor4(h.g, OPEN ? xb[k] : y);
+        }
+        lp += D * 16 * L;
+        sp += D * 16 * L;
+      }
+      x0 = xb[0];
+    }
+    it = nst;
+  }
   for (; it + 1 < iters; it += 2) {
     const uint4 x1 = load_full((uint64_t)(it + 1) * L + q);
     step(it, x0);

@@ -5,11 +5,16 @@
 // (crypto/cipher/e_aesgcmsiv.cc:782-867) and their helpers gcm_siv_keys
 // (:750-780), gcm_siv_polyval (:686-736) and gcm_siv_crypt (:571-601).
 // Design:
-// * 16 lanes per record, 16 records per 256-thread workgroup.
+// * 16 lanes per record; one persistent 768-thread workgroup per CU with 48
+//   record slots (4 per wave).  A wave takes units of 4 records from a
+//   grid-wide counter; everything a record needs happens inside its wave, so
+//   the record loop has wave-local synchronisation only.
+// * Constant-time AES: T0 and T1 replicated 32x in LDS (lane l reads bank l
+//   whatever the index), T2 / T3 = rot16 of them.
 // * Per-record keys: lanes 0..3 (0..5 for AES-256) of a record encrypt
-//   le32(i) || nonce under the master key (T-table AES, tables in LDS) and the
-//   halves are exchanged by shuffles; lane 0 expands the record's encryption
-//   key into the record's LDS slot.
+//   le32(i) || nonce under the master key and the halves are exchanged by
+//   shuffles; the record's lane 0 expands the record's encryption key into
+//   the record's LDS slot.
 // * POLYVAL through GHASH, as the reference computes it (:604-682):
 //   H_g = mulX_GHASH(ByteReverse(H)) and every block byte-reversed -- which in
 //   big-endian words is the block's little-endian words in reverse order, so
@@ -63,47 +68,6 @@ struct Lds {
   uint4 m[kRecs][kPows][16];   // each record's Shoup tables
 };
 static_assert(sizeof(Lds) <= 160 * 1024, "LDS per workgroup");
-
-// Table T_t[x] (T_t = rotl(T0, 8t)).
-__device__ __forceinline__ uint32_t tt(const Lds &L, int t, uint32_t x) {
-  return t == 0 ? t0(L, x) : t == 1 ? t1(L, x) : rotl(t == 2 ? t0(L, x) : t1(L, x), 16);
-}
-
-// Counter-mode caching for the SIV keystream (Bernstein-Schwabe, as gcm.hip):
-// the counter is word 0 + p (little-endian, e_aesgcmsiv.cc:555-580), so within
-// a window of 256 counters only state byte 0 changes.  Round 1 then costs one
-// lookup (column 0's T0) and round 2 four (one per column, from round-1
-// column 0): 5 lookups instead of 32.  The window constants (27 lookups) are
-// rebuilt when the high 24 bits of state word 0 change.
-struct CtrWindow {
-  uint32_t hi = 0xffffffffu;  // (no 24-bit value equals it)
-  uint32_t k0, l0, l1, l2, l3;
-  __device__ __forceinline__ void update(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3,
-                                         const uint4 *rk, const Lds &L) {
-    if ((s0 >> 8) == hi) return;
-    hi = s0 >> 8;
-    const uint4 a = rk[1], c = rk[2];
-    k0 = tt(L, 1, (s1 >> 8) & 0xff) ^ tt(L, 2, (s2 >> 16) & 0xff) ^ tt(L, 3, s3 >> 24) ^ a.x;
-    const uint32_t t1 = tt(L, 0, s1 & 0xff) ^ tt(L, 1, (s2 >> 8) & 0xff) ^
-                        tt(L, 2, (s3 >> 16) & 0xff) ^ tt(L, 3, s0 >> 24) ^ a.y;
-    const uint32_t t2 = tt(L, 0, s2 & 0xff) ^ tt(L, 1, (s3 >> 8) & 0xff) ^
-                        tt(L, 2, (s0 >> 16) & 0xff) ^ tt(L, 3, s1 >> 24) ^ a.z;
-    const uint32_t t3 = tt(L, 0, s3 & 0xff) ^ tt(L, 1, (s0 >> 8) & 0xff) ^
-                        tt(L, 2, (s1 >> 16) & 0xff) ^ tt(L, 3, s2 >> 24) ^ a.w;
-    l0 = tt(L, 1, (t1 >> 8) & 0xff) ^ tt(L, 2, (t2 >> 16) & 0xff) ^ tt(L, 3, t3 >> 24) ^ c.x;
-    l1 = tt(L, 0, t1 & 0xff) ^ tt(L, 1, (t2 >> 8) & 0xff) ^ tt(L, 2, (t3 >> 16) & 0xff) ^ c.y;
-    l2 = tt(L, 0, t2 & 0xff) ^ tt(L, 1, (t3 >> 8) & 0xff) ^ tt(L, 3, t1 >> 24) ^ c.z;
-    l3 = tt(L, 0, t3 & 0xff) ^ tt(L, 2, (t1 >> 16) & 0xff) ^ tt(L, 3, t2 >> 24) ^ c.w;
-  }
-  // Keystream block for state word 0 = s0 (in this window).
-  template <int NR>
-  __device__ __forceinline__ uint4 block(uint32_t s0, const uint4 *rk, const Lds &L) const {
-    const uint32_t t0 = k0 ^ tt(L, 0, s0 & 0xff);
-    return aes_enc_from<NR, 3>(l0 ^ tt(L, 0, t0 & 0xff), l1 ^ tt(L, 3, t0 >> 24),
-                               l2 ^ tt(L, 2, (t0 >> 16) & 0xff), l3 ^ tt(L, 1, (t0 >> 8) & 0xff),
-                               rk, L);
-  }
-};
 
 // ---- GF(2^128) in GCM order, as big-endian words (w0 = bytes 0..3) --------
 

@@ -92,7 +92,10 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_TLS_SET_set_connections", "BSSL_AMD_TLS_SET_clear_connections",
     "BSSL_AMD_TLS_SET_sequences", "BSSL_AMD_TLS_SET_seal_records_device",
     "BSSL_AMD_TLS_SET_open_records_device",
+    "BSSL_AMD_TLS_AEAD_seal_tls13_padded_device", "BSSL_AMD_TLS_AEAD_open_tls13_padded_device",
+    "BSSL_AMD_TLS_SET_seal_tls13_padded_device", "BSSL_AMD_TLS_SET_open_tls13_padded_device",
 ]
+TLS13_TAG_LEN = 16  # BSSL_AMD_TLS13_TAG_LEN: the suffix stride of the padded calls
 TLS1_1_VERSION = 0x0302
 TLS1_2_VERSION = 0x0303
 TLS1_3_VERSION = 0x0304
@@ -143,6 +146,10 @@ class BSSL_AMD_TLS_SET_RECORDS(ctypes.Structure):
         ("records", BSSL_AMD_TLS_RECORDS), ("num_runs", _S), ("run_connection", _P),
         ("run_start", _P),
     ]
+
+
+class BSSL_AMD_TLS13_PADDING(ctypes.Structure):
+    _fields_ = [("pad_lengths", _P), ("pad_block", ctypes.c_uint32)]
 
 
 _CTXP = ctypes.POINTER(EVP_AEAD_CTX)
@@ -215,6 +222,18 @@ _SIGS = {
                                                   _P]),
     "BSSL_AMD_TLS_SET_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
                                                   _P]),
+    "BSSL_AMD_TLS_AEAD_seal_tls13_padded_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_RECORDS),
+                                                        ctypes.POINTER(BSSL_AMD_TLS13_PADDING),
+                                                        _P]),
+    "BSSL_AMD_TLS_AEAD_open_tls13_padded_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_TLS_RECORDS),
+                                                        _P]),
+    "BSSL_AMD_TLS_SET_seal_tls13_padded_device": (_I, [_P,
+                                                       ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
+                                                       ctypes.POINTER(BSSL_AMD_TLS13_PADDING),
+                                                       _P]),
+    "BSSL_AMD_TLS_SET_open_tls13_padded_device": (_I, [_P,
+                                                       ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
+                                                       _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -418,6 +437,17 @@ def _dptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _tls13_padding(pad_lengths, pad_block):
+    """BSSL_AMD_TLS13_PADDING from a device tensor of uint32 / int32 pad
+    lengths (or None) and a block; None when neither asks for padding."""
+    if pad_lengths is None and pad_block in (0, 1):
+        return None
+    pad = BSSL_AMD_TLS13_PADDING()
+    pad.pad_lengths, pad.pad_block = _dptr(pad_lengths), pad_block
+    pad._refs = (pad_lengths,)
+    return pad
+
+
 class TlsAead:
     """BSSL_AMD_TLS_AEAD: one direction of a TLS 1.2 / 1.3 connection (the
     reference's SSLAEADContext) sealing / opening device batches of records."""
@@ -467,6 +497,21 @@ class TlsAead:
                                                           _stream_ptr(stream)):
             _fail("BSSL_AMD_TLS_AEAD_open_records_device")
 
+    def seal_tls13_padded_device(self, recs, pad_lengths=None, pad_block=0, stream=None):
+        """TLS 1.3 records in the padded layout (tls.h): whole fragments in the
+        body, 16-byte tags in the suffix; pad_lengths (device, 4 bytes per
+        record) or pad_block choose the zeros added."""
+        pad = _tls13_padding(pad_lengths, pad_block)
+        if not _lib.BSSL_AMD_TLS_AEAD_seal_tls13_padded_device(
+                self.h, ctypes.byref(recs), None if pad is None else ctypes.byref(pad),
+                _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_AEAD_seal_tls13_padded_device")
+
+    def open_tls13_padded_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_TLS_AEAD_open_tls13_padded_device(self.h, ctypes.byref(recs),
+                                                               _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_AEAD_open_tls13_padded_device")
+
     def close(self):
         if self.h:
             _lib.BSSL_AMD_TLS_AEAD_free(self.h)
@@ -483,8 +528,8 @@ def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, len
                      record_stride=0, record_len=0, types=None, type_=23, status=None,
                      out_lengths=None, explicit_ivs=None):
     """BSSL_AMD_TLS_RECORDS from torch device tensors (keeps references).
-    suffix may be None for a CBC open; out_lengths / explicit_ivs are read for
-    CBC contexts only."""
+    suffix may be None for a CBC open; out_lengths is read for CBC contexts
+    and by the TLS 1.3 padded calls, explicit_ivs for CBC contexts only."""
     r = BSSL_AMD_TLS_RECORDS()
     r.num_records = num_records
     r.in_, r.out = _dptr(inp), _dptr(out)
@@ -556,6 +601,18 @@ class TlsSet:
         if not _lib.BSSL_AMD_TLS_SET_open_records_device(self.h, ctypes.byref(recs),
                                                          _stream_ptr(stream)):
             _fail("BSSL_AMD_TLS_SET_open_records_device")
+
+    def seal_tls13_padded_device(self, recs, pad_lengths=None, pad_block=0, stream=None):
+        pad = _tls13_padding(pad_lengths, pad_block)
+        if not _lib.BSSL_AMD_TLS_SET_seal_tls13_padded_device(
+                self.h, ctypes.byref(recs), None if pad is None else ctypes.byref(pad),
+                _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_seal_tls13_padded_device")
+
+    def open_tls13_padded_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_TLS_SET_open_tls13_padded_device(self.h, ctypes.byref(recs),
+                                                              _stream_ptr(stream)):
+            _fail("BSSL_AMD_TLS_SET_open_tls13_padded_device")
 
     def close(self):
         if self.h:

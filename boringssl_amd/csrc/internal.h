@@ -328,8 +328,55 @@ struct TlsPrepare {
   uint32_t ad_stride;       // 13 (TLS 1.2) or 5 (TLS 1.3)
   int open;                 // records are received: header/explicit nonce read from prefix
   uint8_t *nonces, *prefix, *ad, *extra, *valid;
+  // The TLS 1.3 padded form (tls_pad.hip): `lengths` are fragment lengths F,
+  // extra_len is 0.  Seal: valid[i] is the pre-pass's and is left alone.
+  // Open: the received header's checks go into valid[i].
+  int padded;
+  // Padded seal in a set: the caller's out_lengths (or null), zeroed for a
+  // record that gets no sequence number.
+  uint64_t *out_lengths;
 };
 int launch_tls_prepare(const TlsPrepare &p, void *stream);
+// TLS 1.3 record padding (tls_pad.hip).  The seal pre-pass: from record i's
+// content length, type and padding (pad_lengths[i], or up to a multiple of
+// pad_block; 0 or 1: none) the fragment length -- frag_len[i] = F, valid[i] =
+// 1, out_lengths[i] = F (when given), the content copied when out != in, then
+// the type byte and the zeros; or for a record that cannot be sealed
+// frag_len[i] = the content length, valid[i] = 0, out_lengths[i] = 0.
+struct TlsPadSeal {
+  uint64_t n;
+  const uint8_t *in;
+  uint8_t *out;
+  const uint64_t *offsets;  // or i * record_stride
+  const uint64_t *lengths;  // or record_len for all
+  uint64_t record_stride;
+  uint64_t record_len;
+  const uint8_t *types;     // or `type` for all
+  uint8_t type;
+  const uint32_t *pad_lengths;
+  uint32_t pad_block;
+  uint64_t *frag_len;
+  uint64_t *out_lengths;
+  uint8_t *valid;
+};
+int launch_tls13_pad_seal(const TlsPadSeal &p, void *stream);
+// The open post-pass: for every record with status[i] != 0 the last non-zero
+// byte of the opened fragment goes to types[i] and its index to
+// out_lengths[i]; a fragment of zeros gets status[i] = 0.  Every other record:
+// types[i] = 0, out_lengths[i] = 0.  No pointer may be null but offsets and
+// lengths.
+struct TlsPadStrip {
+  uint64_t n;
+  const uint8_t *out;
+  const uint64_t *offsets;
+  const uint64_t *lengths;  // fragment lengths
+  uint64_t record_stride;
+  uint64_t record_len;
+  uint8_t *status;
+  uint8_t *types;
+  uint64_t *out_lengths;
+};
+int launch_tls13_pad_strip(const TlsPadStrip &p, void *stream);
 // TLS connection sets (tls_set.hip; BSSL_AMD_TLS_SET): the per-connection
 // record-layer state on the device, one entry per slot.  All zero: unset.
 struct alignas(16) TlsSetConn {

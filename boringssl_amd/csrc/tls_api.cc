@@ -7,7 +7,9 @@
 // the records go through the same bulk kernels as any batch (launch_desc).
 // One connection with an AEAD suite, one connection with a CBC suite and a set
 // of many connections differ in what they pass to the shared pieces below:
-// TlsShape, TlsScratch, tls_fill_prepare, tls_batch_desc and tls_launch.
+// TlsShape, TlsScratch, tls_fill_prepare, tls_batch_desc and tls_launch.  The
+// TLS 1.3 padded calls are the same two paths with TlsShape::padded set: a
+// pre-pass before a seal and a strip after an open (tls_pad.hip).
 #include <hip/hip_runtime.h>
 #include <errno.h>
 #include <string.h>
@@ -30,13 +32,29 @@ struct TlsShape {
   bool tls13;
   bool xor_nonce;         // fixed IV XOR seq (TLS 1.3, TLS 1.2 ChaCha) vs fixed || seq
   uint32_t explicit_len;  // 8: TLS 1.2 AES-GCM's explicit nonce; 16: a CBC suite's IV; else 0
+  // The TLS 1.3 padded calls (never set in a context's or a set's own shape):
+  // the body is the whole fragment, type and zeros included, so there is no
+  // extra byte, the suffix is the tag alone and the header length comes from
+  // the fragment length (tls_pad.hip).
+  bool padded = false;
   uint32_t ad_stride() const { return tls13 ? 5 : 13; }
-  uint32_t extra_len() const { return tls13 ? 1 : 0; }  // the inner content type
+  uint32_t extra_len() const { return tls13 && !padded ? 1 : 0; }  // the inner content type
   uint32_t prefix_len() const { return 5 + explicit_len; }
   uint32_t suffix_len(uint32_t tag_len) const { return extra_len() + tag_len; }
   // TLS 1.2 open reports the header type (tls_record.cc:197-235): where to.
   uint8_t *header_types(const BSSL_AMD_TLS_RECORDS *r) const {
     return !seal && !tls13 ? r->types : nullptr;
+  }
+  // The shape of a padded call, or false (error queued) when the context or
+  // set is not TLS 1.3 -- a CBC context's shape never is.
+  bool padded_form(TlsShape *out) const {
+    if (!tls13) {
+      PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+      return false;
+    }
+    *out = *this;
+    out->padded = true;
+    return true;
   }
   // A context or set of the other direction was called.
   bool direction_ok(bool want_seal) const {
@@ -86,29 +104,35 @@ const EVP_AEAD *tls_shape_init(TlsShape *sh, enum evp_aead_direction_t direction
   return rec_aead;
 }
 
-// The scratch of one call, one stream-ordered block: per record the set's key
-// index (4 bytes, first: alignment), the nonce, the AD, the inner type (seal,
-// TLS 1.3; type_len 0: none) and the flag.  Freed in stream order on every path.
+// The scratch of one call, one stream-ordered block: per record a padded
+// call's fragment length (8 bytes) and the set's key index (4 bytes; both
+// first: alignment), the nonce, the AD, the inner type (seal, TLS 1.3;
+// type_len 0: none), the flag, and a padded call's status byte for a caller
+// who passes none.  Freed in stream order on every path.
 struct TlsScratch {
   hipStream_t s;
   uint8_t *buf = nullptr;
+  uint64_t *frag_len = nullptr;
   uint32_t *key_index = nullptr;
-  uint8_t *nonce = nullptr, *ad = nullptr, *type = nullptr, *valid = nullptr;
+  uint8_t *nonce = nullptr, *ad = nullptr, *type = nullptr, *valid = nullptr, *status = nullptr;
   TlsScratch(hipStream_t stream, uint64_t n, uint32_t nonce_len, uint32_t ad_stride,
-             uint32_t type_len, bool keys)
+             uint32_t type_len, bool keys, bool padded = false)
       : s(stream) {
-    const uint32_t key_len = keys ? 4 : 0;
+    const uint32_t key_len = keys ? 4 : 0, frag = padded ? 8 : 0, status_len = padded ? 1 : 0;
     if (hipMallocAsync(reinterpret_cast<void **>(&buf),
-                       n * (key_len + nonce_len + ad_stride + type_len + 1), s) != hipSuccess) {
+                       n * (frag + key_len + nonce_len + ad_stride + type_len + 1 + status_len),
+                       s) != hipSuccess) {
       buf = nullptr;
       PUT_ERROR(ERR_R_MALLOC_FAILURE);
       return;
     }
-    if (keys) key_index = reinterpret_cast<uint32_t *>(buf);
-    nonce = buf + key_len * n;
+    if (padded) frag_len = reinterpret_cast<uint64_t *>(buf);
+    if (keys) key_index = reinterpret_cast<uint32_t *>(buf + frag * n);
+    nonce = buf + (frag + key_len) * n;
     ad = nonce + nonce_len * n;
     type = ad + ad_stride * n;
     valid = type + type_len * n;
+    if (padded) status = valid + n;
   }
   ~TlsScratch() {
     if (buf) hipFreeAsync(buf, s);
@@ -123,10 +147,13 @@ void tls_fill_prepare(TlsPrepare *p, const TlsShape &sh, const BSSL_AMD_TLS_RECO
                       const TlsScratch &sc, uint32_t tag_len) {
   memset(p, 0, sizeof(*p));
   p->n = r->num_records;
-  p->lengths = r->lengths;
+  // (A padded seal's lengths are the pre-pass's fragment lengths.)
+  p->lengths = sh.padded && sh.seal ? sc.frag_len : r->lengths;
   p->record_len = r->record_len;
   p->types = r->types;
   p->type = r->type;
+  p->padded = sh.padded;
+  p->out_lengths = sh.padded && sh.seal ? r->out_lengths : nullptr;
   p->xor_nonce = sh.xor_nonce;
   p->tls13 = sh.tls13;
   p->record_version = 0x0303;  // tls_record_version: TLS 1.3 records say TLS 1.2
@@ -147,6 +174,9 @@ void tls_fill_prepare(TlsPrepare *p, const TlsShape &sh, const BSSL_AMD_TLS_RECO
 // caller has them, nonces (nonce_len bytes), ADs (ad_len bytes) and flags in
 // the scratch, the tags in the suffix slots after the sealed inner type.  One
 // key; a set adds key_index / num_keys, CBC open out_lengths / max_plain_len.
+// A padded seal runs in place on `out`, where the pre-pass has put the
+// fragments, over the fragment lengths in the scratch; a padded open always
+// has a status array, for the strip that follows.
 BatchDesc tls_batch_desc(const BSSL_AMD_TLS_RECORDS *r, const TlsScratch &sc, uint32_t nonce_len,
                          uint32_t ad_len, uint32_t tag_len, const TlsShape &sh) {
   const uint32_t extra_len = sh.extra_len(), suffix_len = sh.suffix_len(tag_len);
@@ -170,6 +200,11 @@ BatchDesc tls_batch_desc(const BSSL_AMD_TLS_RECORDS *r, const TlsScratch &sc, ui
   d.tag_len = tag_len;
   d.num_keys = 1;
   d.valid = sc.valid;
+  if (sh.padded && sh.seal) {
+    d.in = r->out;
+    d.lengths = sc.frag_len;
+  }
+  if (sh.padded && !sh.seal && !d.status) d.status = sc.status;
   if (extra_len) {
     d.extra_len = extra_len;
     if (sh.seal) {  // inner type in, its ciphertext to the suffix
@@ -188,11 +223,19 @@ BatchDesc tls_batch_desc(const BSSL_AMD_TLS_RECORDS *r, const TlsScratch &sc, ui
 }
 
 // The end of every call: the bulk kernels (when the steps before were `ok`),
-// the header types of a TLS 1.2 AEAD-suite open (or null), the error; *seq (one
-// connection, or null) advances only on success.  Returns 1 or 0.
+// the header types of a TLS 1.2 AEAD-suite open (or null), a padded open's
+// strip into types / out_lengths, the error; *seq (one connection, or null)
+// advances only on success.  Returns 1 or 0.
 int tls_launch(bool ok, const KeyMaterial *km, const BatchDesc &d, const TlsShape &sh,
-               uint8_t *header_types, const uint8_t *prefix, uint64_t *seq, void *stream) {
+               uint8_t *header_types, const BSSL_AMD_TLS_RECORDS *r, uint64_t *seq,
+               void *stream) {
+  const uint8_t *prefix = r->prefix;
   ok = ok && launch_desc(km, d, !sh.seal, stream) == 0;
+  if (ok && sh.padded && !sh.seal) {
+    const TlsPadStrip strip = {d.num_records, d.out,    d.offsets, d.lengths,     d.record_stride,
+                               d.record_len,  d.status, r->types,  r->out_lengths};
+    ok = launch_tls13_pad_strip(strip, stream) == 0;
+  }
   if (ok && header_types)
     ok = hipMemcpy2DAsync(header_types, 1, prefix, sh.prefix_len(), 1, d.num_records,
                           hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)) == hipSuccess;
@@ -202,6 +245,47 @@ int tls_launch(bool ok, const KeyMaterial *km, const BatchDesc &d, const TlsShap
   }
   if (seq) *seq += d.num_records;
   return 1;
+}
+
+// A call without its context or set.
+bool present(const void *p) {
+  if (p) return true;
+  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+  return false;
+}
+
+// The null checks of a batch, and for a padded open the two outputs it exists
+// for.  False with the error queued.
+bool tls_records_args_ok(const BSSL_AMD_TLS_RECORDS *r, const TlsShape &sh) {
+  if (r && (r->num_records == 0 ||
+            (r->in && r->out && r->prefix && r->suffix &&
+             !(sh.padded && !sh.seal && (!r->out_lengths || !r->types)))))
+    return true;
+  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+  return false;
+}
+
+// A padded seal's pre-pass (tls_pad.hip): fragment lengths and flags into the
+// scratch, the type bytes and zeros behind the contents in `out`.
+bool tls_pad_seal(const BSSL_AMD_TLS_RECORDS *r, const BSSL_AMD_TLS13_PADDING *pad,
+                  const TlsScratch &sc, void *stream) {
+  TlsPadSeal p;
+  memset(&p, 0, sizeof(p));
+  p.n = r->num_records;
+  p.in = r->in;
+  p.out = r->out;
+  p.offsets = r->offsets;
+  p.lengths = r->lengths;
+  p.record_stride = r->record_stride;
+  p.record_len = r->record_len;
+  p.types = r->types;
+  p.type = r->type;
+  p.pad_lengths = pad ? pad->pad_lengths : nullptr;
+  p.pad_block = pad ? pad->pad_block : 0;
+  p.frag_len = sc.frag_len;
+  p.out_lengths = r->out_lengths;
+  p.valid = sc.valid;
+  return launch_tls13_pad_seal(p, stream) == 0;
 }
 
 }  // namespace
@@ -273,16 +357,13 @@ int tls_cbc_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *s
     d.max_plain_len = kTlsMaxPlainLen;
   }
   // (No header types to copy: on open the prepare kernel wrote them, types_out.)
-  return tls_launch(ok, km, d, sh, nullptr, nullptr, &t->seq, stream);
+  return tls_launch(ok, km, d, sh, nullptr, r, &t->seq, stream);
 }
 
-int tls_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *stream) {
-  if (t && t->cbc) return tls_cbc_records(t, r, stream);
-  if (!t || !r || (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix))) {
-    PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-    return 0;
-  }
-  const TlsShape &sh = t->shape;
+// `sh`: the context's shape, or its padded form (then with `pad` on seal).
+int tls_records(BSSL_AMD_TLS_AEAD *t, const TlsShape &sh, const BSSL_AMD_TLS_RECORDS *r,
+                const BSSL_AMD_TLS13_PADDING *pad, void *stream) {
+  if (!tls_records_args_ok(r, sh)) return 0;
   const uint64_t n = r->num_records;
   if (n == 0) return 1;
   // tls_record.cc:305-308: the sequence number must not wrap.
@@ -300,9 +381,11 @@ int tls_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *strea
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint32_t tag_len = ctx->tag_len;
   // Scratch: nonces (12 B), AD, inner types (seal, TLS 1.3) and flags per record.
-  TlsScratch sc(s, n, 12, sh.ad_stride(), 1, false);
+  TlsScratch sc(s, n, 12, sh.ad_stride(), 1, false, sh.padded);
   if (!sc.buf) return 0;
-  bool ok = hipMemsetAsync(sc.valid, 1, n, s) == hipSuccess;
+  // The flags start at 1, or for a padded seal as its pre-pass leaves them.
+  bool ok = sh.padded && sh.seal ? tls_pad_seal(r, pad, sc, stream)
+                                 : hipMemsetAsync(sc.valid, 1, n, s) == hipSuccess;
   TlsPrepare p;
   tls_fill_prepare(&p, sh, r, sc, tag_len);
   memcpy(p.fixed_iv, t->fixed_iv, 12);
@@ -312,7 +395,7 @@ int tls_records(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r, void *strea
     ok = tls_nonce_scan(sc.nonce, n, ctx->aead->tls, &st->min_next_nonce, &st->mask, sc.valid, 1,
                         stream) == 0;
   return tls_launch(ok, st->km, tls_batch_desc(r, sc, 12, sh.ad_stride(), tag_len, sh), sh,
-                    sh.header_types(r), r->prefix, &t->seq, stream);
+                    sh.header_types(r), r, &t->seq, stream);
 }
 
 }  // namespace
@@ -446,14 +529,31 @@ uint64_t BSSL_AMD_TLS_AEAD_sequence(const BSSL_AMD_TLS_AEAD *t) { return t->seq;
 
 int BSSL_AMD_TLS_AEAD_seal_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
                                           void *hip_stream) {
-  if (t && !t->shape.direction_ok(true)) return 0;
-  return tls_records(t, r, hip_stream);
+  if (!present(t) || !t->shape.direction_ok(true)) return 0;
+  return t->cbc ? tls_cbc_records(t, r, hip_stream)
+                : tls_records(t, t->shape, r, nullptr, hip_stream);
 }
 
 int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
                                           void *hip_stream) {
-  if (t && !t->shape.direction_ok(false)) return 0;
-  return tls_records(t, r, hip_stream);
+  if (!present(t) || !t->shape.direction_ok(false)) return 0;
+  return t->cbc ? tls_cbc_records(t, r, hip_stream)
+                : tls_records(t, t->shape, r, nullptr, hip_stream);
+}
+
+int BSSL_AMD_TLS_AEAD_seal_tls13_padded_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
+                                               const BSSL_AMD_TLS13_PADDING *pad,
+                                               void *hip_stream) {
+  TlsShape sh;
+  if (!present(t) || !t->shape.padded_form(&sh) || !sh.direction_ok(true)) return 0;
+  return tls_records(t, sh, r, pad, hip_stream);
+}
+
+int BSSL_AMD_TLS_AEAD_open_tls13_padded_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
+                                               void *hip_stream) {
+  TlsShape sh;
+  if (!present(t) || !t->shape.padded_form(&sh) || !sh.direction_ok(false)) return 0;
+  return tls_records(t, sh, r, nullptr, hip_stream);
 }
 
 }  // extern "C"
@@ -483,16 +583,16 @@ bool set_range_ok(const BSSL_AMD_TLS_SET *s, size_t first, size_t n) {
   return false;
 }
 
-int tls_set_records(BSSL_AMD_TLS_SET *t, const BSSL_AMD_TLS_SET_RECORDS *sr, void *stream) {
+// `sh`: the set's shape, or its padded form (then with `pad` on seal).
+int tls_set_records(BSSL_AMD_TLS_SET *t, const TlsShape &sh, const BSSL_AMD_TLS_SET_RECORDS *sr,
+                    const BSSL_AMD_TLS13_PADDING *pad, void *stream) {
   const BSSL_AMD_TLS_RECORDS *r = sr ? &sr->records : nullptr;
-  if (!t || !r ||
-      (r->num_records && (!r->in || !r->out || !r->prefix || !r->suffix || sr->num_runs == 0 ||
-                          !sr->run_connection || !sr->run_start)) ||
+  if (!tls_records_args_ok(r, sh)) return 0;
+  if ((r->num_records && (sr->num_runs == 0 || !sr->run_connection || !sr->run_start)) ||
       sr->num_runs > 0xfffffffeu) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return 0;
   }
-  const TlsShape &sh = t->shape;
   const uint64_t n = r->num_records;
   if (n == 0) return 1;
   if (!sh.seal && sh.tls13 && !r->types) {  // open returns the inner types
@@ -503,8 +603,9 @@ int tls_set_records(BSSL_AMD_TLS_SET *t, const BSSL_AMD_TLS_SET_RECORDS *sr, voi
   if (!on_key_device(km)) return 0;
   // Scratch per record: the key index, the nonce (12 B), the AD, the inner
   // type (seal, TLS 1.3) and the flag (tls_set_prepare_kernel writes every one).
-  TlsScratch sc(reinterpret_cast<hipStream_t>(stream), n, 12, sh.ad_stride(), 1, true);
+  TlsScratch sc(reinterpret_cast<hipStream_t>(stream), n, 12, sh.ad_stride(), 1, true, sh.padded);
   if (!sc.buf) return 0;
+  bool ok = !(sh.padded && sh.seal) || tls_pad_seal(r, pad, sc, stream);
   TlsSetPrepare p;
   memset(&p, 0, sizeof(p));
   tls_fill_prepare(&p.rec, sh, r, sc, kSetTagLen);
@@ -514,11 +615,11 @@ int tls_set_records(BSSL_AMD_TLS_SET *t, const BSSL_AMD_TLS_SET_RECORDS *sr, voi
   p.run_connection = sr->run_connection;
   p.run_start = sr->run_start;
   p.key_index = sc.key_index;
-  const bool ok = launch_tls_set_prepare(p, stream) == 0;
+  ok = ok && launch_tls_set_prepare(p, stream) == 0;
   BatchDesc d = tls_batch_desc(r, sc, 12, sh.ad_stride(), kSetTagLen, sh);
   d.key_index = sc.key_index;
   d.num_keys = (uint32_t)km->num_keys;
-  return tls_launch(ok, km, d, sh, sh.header_types(r), r->prefix, nullptr, stream);
+  return tls_launch(ok, km, d, sh, sh.header_types(r), r, nullptr, stream);
 }
 
 }  // namespace
@@ -702,14 +803,28 @@ int BSSL_AMD_TLS_SET_sequences(BSSL_AMD_TLS_SET *s, size_t first, size_t n, uint
 
 int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                          void *hip_stream) {
-  if (s && !s->shape.direction_ok(true)) return 0;
-  return tls_set_records(s, r, hip_stream);
+  if (!present(s) || !s->shape.direction_ok(true)) return 0;
+  return tls_set_records(s, s->shape, r, nullptr, hip_stream);
 }
 
 int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                          void *hip_stream) {
-  if (s && !s->shape.direction_ok(false)) return 0;
-  return tls_set_records(s, r, hip_stream);
+  if (!present(s) || !s->shape.direction_ok(false)) return 0;
+  return tls_set_records(s, s->shape, r, nullptr, hip_stream);
+}
+
+int BSSL_AMD_TLS_SET_seal_tls13_padded_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
+                                              const BSSL_AMD_TLS13_PADDING *pad, void *hip_stream) {
+  TlsShape sh;
+  if (!present(s) || !s->shape.padded_form(&sh) || !sh.direction_ok(true)) return 0;
+  return tls_set_records(s, sh, r, pad, hip_stream);
+}
+
+int BSSL_AMD_TLS_SET_open_tls13_padded_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
+                                              void *hip_stream) {
+  TlsShape sh;
+  if (!present(s) || !s->shape.padded_form(&sh) || !sh.direction_ok(false)) return 0;
+  return tls_set_records(s, sh, r, nullptr, hip_stream);
 }
 
 }  // extern "C"

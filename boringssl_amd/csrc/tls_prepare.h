@@ -32,6 +32,10 @@ struct TlsIv {
 // header and explicit nonce into the prefix, the additional data, the TLS 1.3
 // inner type, and valid[i] = 0 for a plaintext over 2^14 bytes (valid[i] is
 // not written otherwise).  p.fixed_iv and p.seq are not read.
+// The TLS 1.3 padded form (p.padded; tls_pad.hip) differs in what the caller
+// passes -- lengths[i] is the fragment length F and there is no extra byte, so
+// the header says F + 16 -- and in the flag: on seal it is the pre-pass's, on
+// open it takes tls_open_record's checks of the received header.
 __device__ __forceinline__ void tls_prepare_record(const TlsPrepare &p, uint64_t i, uint64_t seq,
                                                    const TlsIv &iv) {
   const uint64_t len = p.lengths ? p.lengths[i] : p.record_len;
@@ -85,7 +89,19 @@ __device__ __forceinline__ void tls_prepare_record(const TlsPrepare &p, uint64_t
     ad[11] = (uint8_t)(len >> 8);
     ad[12] = (uint8_t)len;
   }
-  if (p.tls13 && !p.open) p.extra[i] = type;  // the inner content type (tls_record.cc:272-276)
+  if (p.extra_len && !p.open) p.extra[i] = type;  // the inner content type (tls_record.cc:272-276)
+  if (p.padded) {
+    // Open: application_data outside (tls_record.cc:214), the record version
+    // (:117-130), the stated length (which with the next bound is within
+    // SSL3_RT_MAX_ENCRYPTED_LENGTH, :133), and a fragment of 1 .. 2^14 + 1
+    // bytes (:204-209; an empty one has no type).
+    const uint64_t hlen = ((uint64_t)hdr[3] << 8) | hdr[4];
+    if (p.open && (hdr[0] != 23 || hdr[1] != (uint8_t)(p.record_version >> 8) ||
+                   hdr[2] != (uint8_t)p.record_version || hlen != len + p.tag_len || len == 0 ||
+                   len > kTlsMaxPlainLen + 1))
+      p.valid[i] = 0;
+    return;
+  }
   // Plaintext records are at most 2^14 bytes (SSL3_RT_MAX_PLAIN_LENGTH); a
   // longer one fails like a rejected call.
   if (len > kTlsMaxPlainLen) p.valid[i] = 0;

@@ -82,7 +82,8 @@ __global__ void tls_set_prepare_kernel(TlsSetPrepare p) {
   }
   if (ok) {
     p.key_index[i] = c;
-    p.rec.valid[i] = 1;
+    // (A padded seal's flag is the pre-pass's, tls_pad.hip.)
+    if (!(p.rec.padded && !p.rec.open)) p.rec.valid[i] = 1;
     tls_prepare_record(p.rec, i, seq, iv);
     return;
   }
@@ -94,6 +95,7 @@ __global__ void tls_set_prepare_kernel(TlsSetPrepare p) {
   for (int b = 0; b < 12; b++) p.rec.nonces[12 * i + b] = 0;
   for (uint32_t b = 0; b < p.rec.ad_stride; b++) p.rec.ad[(uint64_t)p.rec.ad_stride * i + b] = 0;
   if (!p.rec.open) {
+    if (p.rec.padded && p.rec.out_lengths) p.rec.out_lengths[i] = 0;
     if (p.rec.tls13) p.rec.extra[i] = 0;
     for (uint32_t b = 0; b < p.rec.prefix_len; b++) p.rec.prefix[(uint64_t)p.rec.prefix_len * i + b] = 0;
   }

@@ -16,7 +16,10 @@
  *              then the 16-byte tag
  * so header ++ prefix-rest ++ body ++ suffix is the wire record.  TLS 1.3
  * records are sealed without padding; open expects unpadded records (the
- * inner type is the byte after the body) and returns it in types[i].
+ * inner type is the byte after the body) and returns it in types[i].  Padded
+ * TLS 1.3 records (RFC 8446 5.4) have calls and a layout of their own:
+ * BSSL_AMD_TLS_AEAD_seal_tls13_padded_device and
+ * BSSL_AMD_TLS_AEAD_open_tls13_padded_device below.
  *
  * The TLS 1.1 / 1.2 AES-CBC-HMAC suites (BSSL_AMD_TLS_AEAD_new_cbc; the
  * reference's SSLAEADContext with a MAC key, ssl_aead_ctx.cc:95-114) have
@@ -149,6 +152,64 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t,
                                                           const BSSL_AMD_TLS_RECORDS *r,
                                                           void *hip_stream);
 
+/* ---- TLS 1.3 record padding (RFC 8446 5.4) --------------------------------
+ *
+ * A TLS 1.3 peer may append zero bytes after the inner content type, and a
+ * receiver strips them (tls_record.cc:198-229).  The padded calls take the
+ * fragment -- the encrypted TLSInnerPlaintext, content || type || zeros -- in
+ * one piece:
+ *   prefix[i]  the 5-byte header
+ *   body       the whole fragment at in/out + offsets[i]
+ *   suffix[i]  the 16-byte tag alone, stride BSSL_AMD_TLS13_TAG_LEN (not
+ *              suffix_len(), which stays the unpadded calls' 17)
+ * so prefix ++ body ++ suffix is the wire record.  Contexts and sets of TLS
+ * 1.3 serve both these and the unpadded calls, on one sequence of numbers.
+ *
+ * Seal: lengths[i] is the content length L.  The fragment has F = L + 1 + P
+ * bytes: P = pad_lengths[i]; or, with pad_block B > 1, F = min(B * ceil((L +
+ * 1) / B), 2^14 + 1); or P = 0 (also for pad == NULL).  The caller leaves room
+ * for F bytes at out + offsets[i]; the ciphertext of content || type || P
+ * zeros goes there (out may equal in; if not, the content is copied), the
+ * header says F + 16 (type 23, version 0x0303; it is the additional data), the
+ * nonce is the unpadded call's, and out_lengths[i], when given, receives F.  A
+ * record fails alone -- status 0, tag and content bytes zeroed, nothing
+ * written past out + offsets[i] + L, out_lengths[i] 0, its sequence number
+ * consumed like an oversize record's -- when L > 2^14, when F > 2^14 + 1 (RFC
+ * 8446 5.4; what a reader enforces, tls_record.cc:204-209), or when its type is
+ * 0, which a reader would take for padding.
+ *
+ * Open: lengths[i] is the received fragment length F (the header's length
+ * minus 16) and suffix[i] the tag.  out_lengths and types are required
+ * (ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED, nothing launched).  With k the index of
+ * the last non-zero byte of the decrypted fragment, types[i] = out[offsets[i]
+ * + k] and out_lengths[i] = k; the bytes from k on stay as decrypted.  A record
+ * fails alone -- status 0, F zero bytes of output, out_lengths[i] 0, types[i]
+ * 0, its sequence number consumed -- when the header's type is not 23
+ * (tls_record.cc:214), its version not 0x0303 (:117-130), its length not F + 16
+ * or F + 16 > 16704 (:133), F > 2^14 + 1 (:204-209), F = 0, the tag is bad, or
+ * the whole fragment is zero (:220-225).
+ *
+ * Argument errors, all before any GPU call: a context or set that is not TLS
+ * 1.3, CBC contexts included (ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED); the wrong
+ * direction (CIPHER_R_INVALID_OPERATION); NULL in, out, prefix or suffix with
+ * records present; a sequence number that would wrap.  The calls only enqueue
+ * work, but the one-connection AES-GCM seal synchronises the stream for its
+ * nonce state like the unpadded one.  In a set the run rules, the failures
+ * that consume no sequence number and the zeroed prefix on seal are those of
+ * the unpadded set calls (below). */
+#define BSSL_AMD_TLS13_TAG_LEN 16
+typedef struct {
+  const uint32_t *pad_lengths; /* device, zero bytes to add to record i; or NULL */
+  uint32_t pad_block;          /* read when pad_lengths == NULL; 0 or 1: no padding */
+} BSSL_AMD_TLS13_PADDING;
+
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_seal_tls13_padded_device(
+    BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
+    const BSSL_AMD_TLS13_PADDING *pad /* NULL: none */, void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_open_tls13_padded_device(BSSL_AMD_TLS_AEAD *t,
+                                                               const BSSL_AMD_TLS_RECORDS *r,
+                                                               void *hip_stream);
+
 /* ---- Connection sets: one record batch across many connections ------------
  *
  * BSSL_AMD_TLS_SET is one direction of up to num_connections connections of
@@ -196,9 +257,8 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t,
  * TLS 1.3 AES-GCM included -- which is what moving a live connection onto the
  * GPU needs.
  *
- * Out of scope: the CBC suites in a set; mixed suites in one set; TLS 1.3
- * padded records on open (as in the one-connection layer); more than one run
- * per connection per call. */
+ * Out of scope: the CBC suites in a set; mixed suites in one set; more than
+ * one run per connection per call. */
 typedef struct bssl_amd_tls_set_st BSSL_AMD_TLS_SET;
 
 /* The version / aead rules and codes of BSSL_AMD_TLS_AEAD_new (TLS 1.2 / 1.3;
@@ -255,6 +315,16 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s,
 BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s,
                                                          const BSSL_AMD_TLS_SET_RECORDS *r,
                                                          void *hip_stream);
+
+/* The TLS 1.3 padded form of the two calls above (see "TLS 1.3 record
+ * padding"): r->records in the padded layout, out_lengths read as there. */
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_seal_tls13_padded_device(BSSL_AMD_TLS_SET *s,
+                                                              const BSSL_AMD_TLS_SET_RECORDS *r,
+                                                              const BSSL_AMD_TLS13_PADDING *pad,
+                                                              void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_open_tls13_padded_device(BSSL_AMD_TLS_SET *s,
+                                                              const BSSL_AMD_TLS_SET_RECORDS *r,
+                                                              void *hip_stream);
 
 #ifdef __cplusplus
 }

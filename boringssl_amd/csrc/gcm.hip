@@ -465,10 +465,10 @@ __device__ __forceinline__ uint4 aes_block_rep(uint4 in, const RoundKeys &rk, co
 // `key` = the batch key (record-end products, finish_record).
 // L = lanes per record (16: 4 records per wave, GHASH stride H^16; 32: 2
 // records per wave, stride H^32 -- the byte table in LDS must be of H^L).
-// RP: rotate the wave's issue priority every iteration ((prio_base + it) mod
-// 4) -- in the tiled path all 16 waves must finish their units together, and
-// with fixed priorities the SIMD arbiter's age order makes the youngest wave
-// of each SIMD ~1.9x slower than the oldest.
+// The wave's issue priority is set per round by the generated statements
+// (gcm_rounds.inc: raised while a round issues its LDS reads).  (Until round
+// 7 the tiled path rotated the priority once per iteration instead; under
+// the per-round window that only cost: config 5 1,096 against 1,112 GiB/s.)
 #ifndef GCM_IOV_HANDOFF
 #define GCM_IOV_HANDOFF 1
 #endif
@@ -520,12 +520,10 @@ static_assert(GCM_STEADY_DEPTH >= 2, "one buffer in use, one in flight");
 // unaligned block spans two lines and the neighbouring lane group wants the
 // rest of each; profiles/r06/s21); the 8-lane aligned path keeps non-temporal
 // loads (temporal: config 2 1,198 against 1,203-1,208, config 5 -0.8 %).
-template <int NR, bool OPEN, bool XT, int L = 16, bool RP = false, bool IOV = false,
-          bool TL = false>
+template <int NR, bool OPEN, bool XT, int L = 16, bool IOV = false, bool TL = false>
 __device__ __forceinline__ void process_records(const RoundKeys &rk, const BatchDesc &b,
                                                 const UnitIn &in, const uint8_t *smem,
-                                                const GcmKeyDev *key, uint32_t lc0, uint32_t lc1,
-                                                int prio_base = 0) {
+                                                const GcmKeyDev *key, uint32_t lc0, uint32_t lc1) {
   static_assert(L == 16 || L == 8 || L == 4, "lanes per record");
   const int q = threadIdx.x & (L - 1);
   const uint64_t rec = in.rec;
@@ -712,14 +710,6 @@ __device__ __forceinline__ void process_records(const RoundKeys &rk, const Batch
   // acc * H^L in h.g.  `uniform` (the steady loop below): the window cache is
   // refreshed by the whole wave when any lane needs it (a scalar branch).
   auto rounds = [&](auto uniform, int it, Gh8 &h) {
-    if constexpr (RP) {
-      switch ((prio_base + it) & 3) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-      }
-    }
     const uint32_t j = (uint32_t)it * L + q;
     const uint32_t ctrn = ctr0 + 1u + (uint32_t)(j + L);  // next block, inc32 mod 2^32
     uint32_t xs = bswap32(ctrn) ^ rk.w[0][3];
@@ -910,8 +900,7 @@ __global__ __launch_bounds__(1024) void gcm_kernel(const GcmKeyDev *__restrict__
     if (first >= hi) break;
     UnitIn in;
     unit_load<XT, IOV>(in, b, first + lane / L, lane & (L - 1), hi);
-    process_records<NR, OPEN, XT, L, false, IOV, L == 4 || L == 16>(rk, b, in, smem, keys, lc0,
-                                                                     lc1);
+    process_records<NR, OPEN, XT, L, IOV, L == 4 || L == 16>(rk, b, in, smem, keys, lc0, lc1);
   }
 }
 
@@ -924,9 +913,6 @@ __global__ __launch_bounds__(1024) void gcm_kernel(const GcmKeyDev *__restrict__
 // finishes its tiles early takes the next one instead of idling at the end.
 #ifndef GCM_KEYSET_DYN
 #define GCM_KEYSET_DYN 1
-#endif
-#ifndef GCM_KEYSET_RP
-#define GCM_KEYSET_RP 1  // (A/B: 0 = no per-iteration priority rotation)
 #endif
 template <int NR, bool OPEN, bool XT, int W>
 __global__ __launch_bounds__(1024) void gcm_keyset_kernel(const GcmKeyDev *__restrict__ keys,
@@ -1003,9 +989,7 @@ __global__ __launch_bounds__(1024) void gcm_keyset_kernel(const GcmKeyDev *__res
       const bool active = (mask >> t) & 1;
       UnitIn in;
       unit_load<XT, false>(in, b, active ? base + t : n, lane & 15, n);
-      process_records<NR, OPEN, XT, 16, GCM_KEYSET_RP != 0>(rk, b, in, smem, keys + k, lc0, lc1,
-                                                           wave >> 2);
-      __builtin_amdgcn_s_setprio(0);
+      process_records<NR, OPEN, XT, 16>(rk, b, in, smem, keys + k, lc0, lc1);
     }
   }
 }

@@ -14,6 +14,11 @@
 // each record's E_K(J0) at its end with the T-tables' quad form (ek0_quad),
 // so no batched E_K(J0) production is needed.  DESIGN.md §9.1.
 #define BSSL_AMD_MIX_TU 1
+// No per-round priority window here (gcm_rounds.inc): its s_setprio 0 would
+// drop the T-table waves below the bitsliced waves, which the priority set
+// in gcm_mix_kernel is there to prevent.
+#undef GCM_ROUND_PRIO
+#define GCM_ROUND_PRIO 0
 #include "gcm.hip"
 #include "gcm_bs.hip"
 
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(1024) void gcm_mix_kernel(const GcmKeyDev *__restri
     } else {
       UnitIn in;
       unit_load<false, false>(in, b, first + lane / 16, lane & 15, n);
-      process_records<NR, OPEN, false, 16, false, false>(rk, b, in, smem, keys, lc0, lc1);
+      process_records<NR, OPEN, false, 16, false>(rk, b, in, smem, keys, lc0, lc1);
     }
   }
 }

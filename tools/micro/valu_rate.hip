@@ -16,6 +16,12 @@ constexpr int kIters = 256;
                : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), \
                  "+v"(r[6]), "+v"(r[7]) : "v"(a), "v"(b) : "s40", "s41");
 
+// The same with an SGPR operand (%10), as the GCM rounds hold their masks.
+#define BODY8S(INSN)                                                  \
+  asm volatile(INSN(0) INSN(1) INSN(2) INSN(3) INSN(4) INSN(5) INSN(6) INSN(7) \
+               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), \
+                 "+v"(r[6]), "+v"(r[7]) : "v"(a), "v"(b), "s"(sm));
+
 // 64-bit register pairs for the mad/shift cases.
 #define BODY8_64(INSN)                                                  \
   asm volatile(INSN(0) INSN(1) INSN(2) INSN(3) INSN(4) INSN(5) INSN(6) INSN(7) \
@@ -40,6 +46,33 @@ constexpr int kIters = 256;
 #define I_XOR_SDWA(i) "v_xor_b32_sdwa %" #i ", %" #i ", %8 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_0\n"
 #define I_PK_ADD16(i) "v_pk_add_u16 %" #i ", %" #i ", %8 op_sel:[1,1] op_sel_hi:[0,0]\n"
 
+// Address forms of the GCM T-table lookups (a state byte into bits 8..15 over
+// a lane constant): bitop3 with its mask in an SGPR, SDWA byte moves into
+// byte 1 of a register that keeps its other bytes (chain through the
+// preserved destination), and the three-operand mask/insert/extract ops.
+#define I_BITOP3_S(i) "v_bitop3_b32 %" #i ", %" #i ", %10, %9 bitop3:0xea\n"
+// (which of the two makes the case above slow: the SGPR or the truth table;
+// and whether an SGPR source slows a VOP2 op as well)
+#define I_BITOP3_S96(i) "v_bitop3_b32 %" #i ", %" #i ", %8, %10 bitop3:0x96\n"
+#define I_BITOP3_VSEL(i) "v_bitop3_b32 %" #i ", %" #i ", %8, %9 bitop3:0xdc\n"
+#define I_XOR_S(i) "v_xor_b32 %" #i ", %10, %" #i "\n"
+#define I_MOV_SDWA0(i) "v_mov_b32_sdwa %" #i ", %8 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0\n"
+#define I_MOV_SDWA2(i) "v_mov_b32_sdwa %" #i ", %8 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2\n"
+#define I_MOV_SDWA3(i) "v_mov_b32_sdwa %" #i ", %8 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_3\n"
+// (as the rounds would use it: one register rewritten by every instruction,
+// each from another source register)
+#define I_MOV_SDWA_ONE(i) "v_mov_b32_sdwa %0, %" #i " dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2\n"
+#define I_OR_SDWA(i) "v_or_b32_sdwa %" #i ", %" #i ", %8 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_2 src1_sel:DWORD\n"
+#define I_BFI(i) "v_bfi_b32 %" #i ", %9, %" #i ", %8\n"
+#define I_AND_OR(i) "v_and_or_b32 %" #i ", %" #i ", %9, %8\n"
+#define I_BFE(i) "v_bfe_u32 %" #i ", %" #i ", 8, 8\n"
+// v_readlane_b32 writes an SGPR: eight destinations (s40..s47), sources the
+// eight chain registers; nothing reads the results inside the stream.
+#define I_READLANE(i) "v_readlane_b32 s4" #i ", %" #i ", 3\n"
+#define BODY8_RL asm volatile(I_READLANE(0) I_READLANE(1) I_READLANE(2) I_READLANE(3) I_READLANE(4) I_READLANE(5) I_READLANE(6) I_READLANE(7) \
+               : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), \
+                 "+v"(r[6]), "+v"(r[7]) : "v"(a), "v"(b) : "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47");
+
 // ChaCha quarter-round-like dependent triples (add, xor, rotate) on ILP
 // independent chains.
 #define QSTEP(i) "v_add_u32 %" #i ", %" #i ", %8\n v_xor_b32 %" #i ", %" #i ", %9\n v_alignbit_b32 %" #i ", %" #i ", %" #i ", 16\n"
@@ -48,6 +81,7 @@ constexpr int kIters = 256;
 
 template <int K>
 __global__ void rate(uint64_t *out, uint32_t a, uint32_t b) {
+  const uint32_t sm = __builtin_amdgcn_readfirstlane(b) | 0xff00u;  // an SGPR operand
   uint32_t r[8];
   uint64_t w[8];
   for (int i = 0; i < 8; i++) { r[i] = threadIdx.x + i; w[i] = threadIdx.x * 3ull + i; }
@@ -78,6 +112,19 @@ __global__ void rate(uint64_t *out, uint32_t a, uint32_t b) {
     if (K == 17) { QBODY4 QBODY4 asm volatile("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n" : "+v"(r[5]) : "v"(a)); }
     if (K == 19) { BODY8(I_XOR_SDWA) BODY8(I_XOR_SDWA) BODY8(I_XOR_SDWA) BODY8(I_XOR_SDWA) }
     if (K == 20) { BODY8(I_PK_ADD16) BODY8(I_PK_ADD16) BODY8(I_PK_ADD16) BODY8(I_PK_ADD16) }
+    if (K == 21) { BODY8S(I_BITOP3_S) BODY8S(I_BITOP3_S) BODY8S(I_BITOP3_S) BODY8S(I_BITOP3_S) }
+    if (K == 22) { BODY8(I_MOV_SDWA0) BODY8(I_MOV_SDWA0) BODY8(I_MOV_SDWA0) BODY8(I_MOV_SDWA0) }
+    if (K == 23) { BODY8(I_MOV_SDWA2) BODY8(I_MOV_SDWA2) BODY8(I_MOV_SDWA2) BODY8(I_MOV_SDWA2) }
+    if (K == 24) { BODY8(I_MOV_SDWA3) BODY8(I_MOV_SDWA3) BODY8(I_MOV_SDWA3) BODY8(I_MOV_SDWA3) }
+    if (K == 25) { BODY8(I_MOV_SDWA_ONE) BODY8(I_MOV_SDWA_ONE) BODY8(I_MOV_SDWA_ONE) BODY8(I_MOV_SDWA_ONE) }
+    if (K == 26) { BODY8(I_OR_SDWA) BODY8(I_OR_SDWA) BODY8(I_OR_SDWA) BODY8(I_OR_SDWA) }
+    if (K == 27) { BODY8(I_BFI) BODY8(I_BFI) BODY8(I_BFI) BODY8(I_BFI) }
+    if (K == 28) { BODY8(I_AND_OR) BODY8(I_AND_OR) BODY8(I_AND_OR) BODY8(I_AND_OR) }
+    if (K == 29) { BODY8(I_BFE) BODY8(I_BFE) BODY8(I_BFE) BODY8(I_BFE) }
+    if (K == 30) { BODY8_RL BODY8_RL BODY8_RL BODY8_RL }
+    if (K == 31) { BODY8S(I_BITOP3_S96) BODY8S(I_BITOP3_S96) BODY8S(I_BITOP3_S96) BODY8S(I_BITOP3_S96) }
+    if (K == 32) { BODY8(I_BITOP3_VSEL) BODY8(I_BITOP3_VSEL) BODY8(I_BITOP3_VSEL) BODY8(I_BITOP3_VSEL) }
+    if (K == 33) { BODY8S(I_XOR_S) BODY8S(I_XOR_S) BODY8S(I_XOR_S) BODY8S(I_XOR_S) }
     if (K == 18) { QBODY8 asm volatile("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %1\n" : "+v"(r[5]) : "v"(a)); }
   }
   const uint64_t t1 = __builtin_amdgcn_s_memtime();
@@ -92,7 +139,10 @@ int main() {
                          "v_mul_hi_u32", "v_mad_u64_u32", "v_lshrrev_b64", "v_lshl_add_u64",
                          "v_perm_b32", "v_alignbyte_b32", "v_lshl_or_b32", "v_xad_u32", "v_add3_u32",
                          "v_lshlrev_b32", "v_xor_b32 ~0", "v_alignbit(0)", "QR ILP4(+8 add)", "QR ILP8(+8 add)",
-                         "v_xor_b32_sdwa", "v_pk_add_u16"};
+                         "v_xor_b32_sdwa", "v_pk_add_u16", "v_bitop3 (SGPR)", "v_mov_sdwa B0>B1",
+                         "v_mov_sdwa B2>B1", "v_mov_sdwa B3>B1", "v_mov_sdwa 1dst", "v_or_b32_sdwa",
+                         "v_bfi_b32", "v_and_or_b32", "v_bfe_u32", "v_readlane_b32",
+                         "v_bitop3 SGPR 96", "v_bitop3 VGPR dc", "v_xor_b32 (SGPR)"};
   uint64_t *d;
   CK(hipMalloc(&d, 1 << 20));
   uint64_t h[4096];
@@ -100,7 +150,7 @@ int main() {
   // same occupancy is reported beside them.
   for (int waves = 1; waves <= 4; waves *= 4) {
     double base = 0;
-    for (int k = 0; k < 21; k++) {
+    for (int k = 0; k < 34; k++) {
       for (int rep = 0; rep < 2; rep++) {
         // one workgroup per CU, `waves` waves per SIMD
         const int threads = 256 * waves;
@@ -126,6 +176,19 @@ int main() {
           case 18: rate<18><<<256, threads>>>(d, 3, 5); break;
           case 19: rate<19><<<256, threads>>>(d, 3, 5); break;
           case 20: rate<20><<<256, threads>>>(d, 3, 5); break;
+          case 21: rate<21><<<256, threads>>>(d, 3, 5); break;
+          case 22: rate<22><<<256, threads>>>(d, 3, 5); break;
+          case 23: rate<23><<<256, threads>>>(d, 3, 5); break;
+          case 24: rate<24><<<256, threads>>>(d, 3, 5); break;
+          case 25: rate<25><<<256, threads>>>(d, 3, 5); break;
+          case 26: rate<26><<<256, threads>>>(d, 3, 5); break;
+          case 27: rate<27><<<256, threads>>>(d, 3, 0x00ff00ff); break;
+          case 28: rate<28><<<256, threads>>>(d, 3, 0x00ff00ff); break;
+          case 29: rate<29><<<256, threads>>>(d, 3, 5); break;
+          case 30: rate<30><<<256, threads>>>(d, 3, 5); break;
+          case 31: rate<31><<<256, threads>>>(d, 3, 5); break;
+          case 32: rate<32><<<256, threads>>>(d, 0x1ff7c, 0x100fc); break;
+          case 33: rate<33><<<256, threads>>>(d, 3, 5); break;
         }
         CK(hipDeviceSynchronize());
       }

@@ -94,11 +94,17 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_TLS_SET_open_records_device",
     "BSSL_AMD_TLS_AEAD_seal_tls13_padded_device", "BSSL_AMD_TLS_AEAD_open_tls13_padded_device",
     "BSSL_AMD_TLS_SET_seal_tls13_padded_device", "BSSL_AMD_TLS_SET_open_tls13_padded_device",
+    "BSSL_AMD_DTLS_AEAD_new", "BSSL_AMD_DTLS_AEAD_free", "BSSL_AMD_DTLS_AEAD_prefix_len",
+    "BSSL_AMD_DTLS_AEAD_sequence", "BSSL_AMD_DTLS_AEAD_get_window",
+    "BSSL_AMD_DTLS_AEAD_set_window", "BSSL_AMD_DTLS_AEAD_seal_records_device",
+    "BSSL_AMD_DTLS_AEAD_open_records_device",
 ]
 TLS13_TAG_LEN = 16  # BSSL_AMD_TLS13_TAG_LEN: the suffix stride of the padded calls
 TLS1_1_VERSION = 0x0302
 TLS1_2_VERSION = 0x0303
 TLS1_3_VERSION = 0x0304
+DTLS1_2_VERSION = 0xfefd
+DTLS1_3_VERSION = 0xfefc
 
 
 class EVP_AEAD_CTX(ctypes.Structure):
@@ -138,6 +144,15 @@ class BSSL_AMD_TLS_RECORDS(ctypes.Structure):
         ("type", ctypes.c_uint8), ("prefix", _P), ("suffix", _P), ("status", _P),
         # read for CBC contexts only (TlsAead.new_cbc)
         ("out_lengths", _P), ("explicit_ivs", _P),
+    ]
+
+
+class BSSL_AMD_DTLS_RECORDS(ctypes.Structure):
+    _fields_ = [
+        ("num_records", _S), ("in_", _P), ("out", _P), ("offsets", _P), ("lengths", _P),
+        ("record_stride", ctypes.c_uint64), ("record_len", ctypes.c_uint64), ("types", _P),
+        ("type", ctypes.c_uint8), ("prefix", _P), ("suffix", _P), ("status", _P),
+        ("out_lengths", _P), ("record_numbers", _P),
     ]
 
 
@@ -234,6 +249,17 @@ _SIGS = {
     "BSSL_AMD_TLS_SET_open_tls13_padded_device": (_I, [_P,
                                                        ctypes.POINTER(BSSL_AMD_TLS_SET_RECORDS),
                                                        _P]),
+    "BSSL_AMD_DTLS_AEAD_new": (_P, [_I, ctypes.c_uint16, _P, _P, _S, _P, _S, _P, _S,
+                                    ctypes.c_uint16, ctypes.c_uint64]),
+    "BSSL_AMD_DTLS_AEAD_free": (None, [_P]),
+    "BSSL_AMD_DTLS_AEAD_prefix_len": (_S, [_P]),
+    "BSSL_AMD_DTLS_AEAD_sequence": (ctypes.c_uint64, [_P]),
+    "BSSL_AMD_DTLS_AEAD_get_window": (_I, [_P, ctypes.POINTER(ctypes.c_uint64), _P, _P]),
+    "BSSL_AMD_DTLS_AEAD_set_window": (_I, [_P, ctypes.c_uint64, _P, _P]),
+    "BSSL_AMD_DTLS_AEAD_seal_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_RECORDS),
+                                                    _P]),
+    "BSSL_AMD_DTLS_AEAD_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_RECORDS),
+                                                    _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -539,6 +565,85 @@ def make_tls_records(num_records, inp, out, prefix, suffix, *, offsets=None, len
     r.prefix, r.suffix, r.status = _dptr(prefix), _dptr(suffix), _dptr(status)
     r.out_lengths, r.explicit_ivs = _dptr(out_lengths), _dptr(explicit_ivs)
     r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status, out_lengths, explicit_ivs)
+    return r
+
+
+class DtlsAead:
+    """BSSL_AMD_DTLS_AEAD: one direction of one epoch of a DTLS 1.2 / 1.3
+    association sealing / opening device batches of records; an opening
+    context keeps the anti-replay window on the device (tls.h)."""
+
+    def __init__(self, direction, version, aead, key, fixed_iv, sn_key=None, epoch=1, seq=0):
+        if isinstance(aead, str):
+            aead = EVP_aead(aead)
+        key, fixed_iv = bytes(key), bytes(fixed_iv)
+        sn_key = None if sn_key is None else bytes(sn_key)
+        self.h = _lib.BSSL_AMD_DTLS_AEAD_new(direction, version, aead, key, len(key), fixed_iv,
+                                             len(fixed_iv), sn_key,
+                                             0 if sn_key is None else len(sn_key), epoch, seq)
+        if not self.h:
+            _fail("BSSL_AMD_DTLS_AEAD_new")
+
+    @property
+    def prefix_len(self):
+        return _lib.BSSL_AMD_DTLS_AEAD_prefix_len(self.h)
+
+    @property
+    def sequence(self):
+        return _lib.BSSL_AMD_DTLS_AEAD_sequence(self.h)
+
+    def get_window(self, stream=None):
+        """(max_seq, the 32-byte bitmap): bit k = max_seq - k seen (synchronises)."""
+        max_seq = ctypes.c_uint64(0)
+        bitmap = ctypes.create_string_buffer(32)
+        if not _lib.BSSL_AMD_DTLS_AEAD_get_window(self.h, ctypes.byref(max_seq), bitmap,
+                                                  _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_AEAD_get_window")
+        return max_seq.value, bitmap.raw
+
+    def set_window(self, max_seq, bitmap=bytes(32), stream=None):
+        bitmap = bytes(bitmap)
+        if len(bitmap) != 32:
+            raise ValueError("the bitmap has 32 bytes")
+        if not _lib.BSSL_AMD_DTLS_AEAD_set_window(self.h, max_seq, bitmap, _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_AEAD_set_window")
+
+    def seal_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_DTLS_AEAD_seal_records_device(self.h, ctypes.byref(recs),
+                                                           _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_AEAD_seal_records_device")
+
+    def open_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_DTLS_AEAD_open_records_device(self.h, ctypes.byref(recs),
+                                                           _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_AEAD_open_records_device")
+
+    def close(self):
+        if self.h:
+            _lib.BSSL_AMD_DTLS_AEAD_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
+def make_dtls_records(num_records, inp, out, prefix, suffix, *, offsets=None, lengths=None,
+                      record_stride=0, record_len=0, types=None, type_=23, status=None,
+                      out_lengths=None, record_numbers=None):
+    """BSSL_AMD_DTLS_RECORDS from torch device tensors (keeps references)."""
+    r = BSSL_AMD_DTLS_RECORDS()
+    r.num_records = num_records
+    r.in_, r.out = _dptr(inp), _dptr(out)
+    r.offsets, r.lengths = _dptr(offsets), _dptr(lengths)
+    r.record_stride, r.record_len = record_stride, record_len
+    r.types, r.type = _dptr(types), type_
+    r.prefix, r.suffix, r.status = _dptr(prefix), _dptr(suffix), _dptr(status)
+    r.out_lengths, r.record_numbers = _dptr(out_lengths), _dptr(record_numbers)
+    r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status, out_lengths,
+               record_numbers)
     return r
 
 

@@ -270,6 +270,8 @@ bool on_key_device(const KeyMaterial *km) {
 
 size_t tls_cbc_mac_len(const EVP_AEAD *aead) { return aead->max_tag_len; }
 
+const KernelEvents *kernel_timing_pair() { return timing_pair(); }
+
 uint64_t load_be64(const uint8_t *p) {
   uint64_t v = 0;
   for (int i = 0; i < 8; i++) v = (v << 8) | p[i];

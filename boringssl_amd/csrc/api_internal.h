@@ -77,6 +77,11 @@ void free_keys(KeyMaterial *km);
 // this batch (-1: read it here), so one batch never sees two engines.
 int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stream,
                 int gcm_eng = -1);
+// With BSSL_AMD_set_kernel_timing on: a pair of events for a kernel that frames
+// the bulk one (dtls_api.cc), reported by BSSL_AMD_collect_kernel_times in
+// launch order with the bulk kernels' pairs; null otherwise.  The pointer holds
+// until the next pair is taken.
+const KernelEvents *kernel_timing_pair();
 // kAeadTlsCbc: the MAC size (e_tls.cc:105-116).
 size_t tls_cbc_mac_len(const EVP_AEAD *aead);
 uint64_t load_be64(const uint8_t *p);

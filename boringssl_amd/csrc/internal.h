@@ -431,6 +431,98 @@ struct TlsCbcPrepare {
   uint8_t *types_out;           // open: receives the header types, or null
 };
 int launch_tls_cbc_prepare(const TlsCbcPrepare &p, void *stream);
+// DTLS record protection (dtls.hip, dtls_prepare.h; BSSL_AMD_DTLS_AEAD): what
+// one direction of one epoch keeps on the device.
+struct alignas(16) DtlsState {
+  // The read window (DTLSReplayBitmap, dtls_record.cc:29-57): bit k of the
+  // 256-bit map (word k / 64, bit k % 64) = sequence number max_seq - k seen.
+  uint64_t max_seq;
+  uint64_t bitmap[4];
+  uint64_t pad;
+  // DTLS 1.3: the record-number key -- the FIPS-197 schedule as little-endian
+  // words, unrotated (AES suites), or the ChaCha20 key's eight words in
+  // sn[0..7].
+  uint32_t sn[60];
+  uint32_t pad2[4];
+};
+static_assert(sizeof(DtlsState) == 48 + 256, "layout");
+// How a DTLS 1.3 context computes the record-number mask (RFC 9147 4.2.3).
+enum DtlsMask : int { kDtlsMaskNone = 0, kDtlsMaskAes128 = 1, kDtlsMaskAes256 = 2, kDtlsMaskChaCha = 3 };
+constexpr uint64_t kDtlsMaxSequence = (uint64_t(1) << 48) - 1;
+// Step 1 of a batch (dtls_prepare_kernel), one lane per record.  Seal: the
+// header (and DTLS 1.2 AES-GCM's explicit nonce) into the prefix, zeros for a
+// record that fails; nonce and AD into the scratch; record_numbers[i].  Open:
+// the received header's checks into valid[i], the header type (DTLS 1.2), the
+// sequence number (DTLS 1.3: unmasked and reconstructed against the window's
+// maximum), nonce, AD and its length, seqs[i] and record_numbers[i].
+struct DtlsPrepare {
+  uint64_t n;
+  const uint8_t *body;      // open, DTLS 1.3: the fragments (the mask's sample)
+  const uint64_t *offsets;  // or i * record_stride
+  const uint64_t *lengths;  // or record_len for all; DTLS 1.3: fragment lengths
+  uint64_t record_stride;
+  uint64_t record_len;
+  const uint8_t *types;     // seal, DTLS 1.2: or `type` for all
+  uint8_t type;
+  uint8_t *types_out;       // open, DTLS 1.2: receives the header types, or null
+  uint8_t fixed_iv[12];
+  uint16_t epoch;
+  uint64_t seq;             // seal: the first record's sequence number
+  int open;
+  int dtls13;
+  int xor_nonce;            // fixed_iv XOR sequence vs the 4-byte IV || explicit nonce
+  uint32_t prefix_len;      // 13, 21 or 5
+  uint32_t ad_stride;       // 13 or 5
+  uint8_t *prefix;
+  const uint8_t *suffix;    // the tags (open, DTLS 1.3: the sample's continuation)
+  uint8_t *nonces, *ad, *valid;
+  uint64_t *ad_lengths;     // open, DTLS 1.3: 2 to 5
+  uint64_t *seqs;           // open: the records' sequence numbers, for the window
+  uint64_t *record_numbers; // or null
+  uint64_t *out_lengths;    // seal, DTLS 1.2: the body length or 0 (failed); or null
+  const DtlsState *state;
+};
+int launch_dtls_prepare(const DtlsPrepare &p, int mask, void *stream);
+// After a DTLS 1.3 seal: header bytes 1..2 of every record with status[i] != 0
+// XOR the first two mask bytes; the sample is the first 16 bytes of fragment ||
+// tag.
+struct DtlsMaskSeal {
+  uint64_t n;
+  const uint8_t *body;
+  const uint64_t *offsets;
+  const uint64_t *lengths;  // fragment lengths
+  uint64_t record_stride;
+  uint64_t record_len;
+  uint8_t *prefix;          // 5 bytes per record
+  const uint8_t *suffix;    // 16 bytes per record
+  const uint8_t *status;
+  const DtlsState *state;
+};
+int launch_dtls_mask(const DtlsMaskSeal &p, int mask, void *stream);
+// Step 3 of an open: the replay window over the records with status[i] != 0,
+// in index order, as three launches (dtls.hip).  A record the window refuses
+// gets status 0, lengths[i] zero bytes of output, out_lengths[i] 0 and (DTLS
+// 1.3) types[i] 0.  table: 2 * table_slots uint64 (all ones), block_max: one
+// uint64 per 256 records, old: 5 uint64 -- scratch.
+struct DtlsWindow {
+  uint64_t n;
+  uint8_t *out;
+  const uint64_t *offsets;
+  const uint64_t *lengths;
+  uint64_t record_stride;
+  uint64_t record_len;
+  uint8_t *status;
+  uint64_t *out_lengths;  // or null
+  int set_lengths;        // DTLS 1.2: out_lengths[i] = lengths[i] for an accepted record
+  uint8_t *types;         // DTLS 1.3, or null
+  const uint64_t *seqs;
+  uint64_t *table;
+  uint64_t table_slots;   // a power of two, at least 2 n
+  uint64_t *block_max;
+  uint64_t *old;
+  DtlsState *state;
+};
+int launch_dtls_window(const DtlsWindow &p, void *stream);
 // Record-layer limits (include/openssl/ssl3.h of the reference).
 constexpr uint64_t kTlsMaxPlainLen = 16384;
 constexpr uint64_t kTlsMaxEncryptedLen = 16384 + 320;

@@ -58,13 +58,16 @@ __device__ __forceinline__ uint32_t span16(uint64_t total, uint64_t at) {
   return at >= total ? 0u : total - at < 16 ? (uint32_t)(total - at) : 16u;
 }
 
-// The first n bytes of v (n <= 16), the rest zero.
+// The first n bytes of v (n <= 16), the rest zero.  (iov_dev.h has the same
+// function: a file that includes it first, dtls.hip, takes that one.)
+#ifndef BSSL_AMD_IOV_DEV_H
 __device__ __forceinline__ uint4 mask_block(uint4 v, uint32_t n) {
   auto m = [&](uint32_t lo) {
     return n >= lo + 4 ? 0xffffffffu : n <= lo ? 0u : (1u << (8 * (n - lo))) - 1u;
   };
   return make_uint4(v.x & m(0), v.y & m(4), v.z & m(8), v.w & m(12));
 }
+#endif
 
 // v with byte i (< 16) OR-ed with `val`.
 __device__ __forceinline__ uint4 or_byte(uint4 v, uint32_t i, uint32_t val) {

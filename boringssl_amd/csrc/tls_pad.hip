@@ -25,17 +25,12 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "wave_bytes.h"
 
 namespace bssl_amd {
 namespace {
 
 constexpr uint64_t kTls13MaxFragment = kTlsMaxPlainLen + 1;  // content, type and padding
-
-__device__ __forceinline__ uint64_t bcast64(uint64_t v, int lane) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane);
-  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane);
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // A mask of bytes [a, b) of the 32-bit word that holds bytes [4w, 4w + 4) of a
 // 16-byte word; a and b are positions in the 16-byte word, 0 <= a, b <= 16.
@@ -62,20 +57,6 @@ __device__ __forceinline__ int last_nonzero(uint4 v, int a, int b, uint32_t *byt
   }
   *byte = val;
   return pos;
-}
-
-// The wave zeroes bytes [0, n) at p (wave-uniform): whole aligned 16-byte
-// words where they lie inside, single bytes in the two words at the ends.
-__device__ __forceinline__ void wave_zero(uint8_t *p, uint64_t n, int lane) {
-  const uint64_t head = (uintptr_t)p & 15;
-  uint8_t *base = p - head;
-  for (uint64_t q = lane; 16 * q < head + n; q += 64) {
-    const uint64_t lo = max(16 * q, head), hi = min(16 * q + 16, head + n);
-    if (hi - lo == 16)
-      *reinterpret_cast<uint4 *>(base + 16 * q) = make_uint4(0, 0, 0, 0);
-    else
-      for (uint64_t x = lo; x < hi; x++) base[x] = 0;
-  }
 }
 
 // The wave copies n bytes (wave-uniform): in aligned 16-byte words when source

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "chacha_block.h"
 #include "tls_prepare.h"
 
 namespace bssl_amd {
@@ -39,23 +40,10 @@ __device__ void chacha_iv(const uint32_t (&key)[8], uint64_t seq, uint8_t *iv) {
   in[13] = (uint32_t)(seq >> 32);
   in[14] = 0;
   in[15] = 0;
-  uint32_t x[16];
-  for (int k = 0; k < 16; k++) x[k] = in[k];
-  auto rotl = [](uint32_t v, int c) { return (v << c) | (v >> (32 - c)); };
-  auto qr = [&](int a, int b, int c, int d) {
-    x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16);
-    x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12);
-    x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8);
-    x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7);
-  };
-  for (int r = 0; r < 10; r++) {
-    qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15);
-    qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14);
-  }
-  for (int k = 0; k < 4; k++) {
-    const uint32_t v = x[k] + in[k];
-    for (int j = 0; j < 4; j++) iv[4 * k + j] = (uint8_t)(v >> (8 * j));
-  }
+  uint32_t head[4];
+  chacha20_block_head(in, head);
+  for (int k = 0; k < 4; k++)
+    for (int j = 0; j < 4; j++) iv[4 * k + j] = (uint8_t)(head[k] >> (8 * j));
 }
 
 // The CBC suites (TLS 1.1 / 1.2, explicit IV): SSLAEADContext::SealScatter /

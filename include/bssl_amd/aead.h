@@ -410,7 +410,9 @@ BSSL_AMD_EXPORT int BSSL_AMD_synth_fill_device(uint64_t first_record, size_t n,
  * synchronisation).  BSSL_AMD_collect_kernel_times waits for the recorded
  * launches, writes up to `max` durations (ms) in launch order and returns how
  * many launches were pending.  last_kernel_ms / _name describe the most
- * recent one. */
+ * recent one.  The DTLS record calls (tls.h) also bracket the steps around
+ * their bulk kernel, in launch order: seal -- prepare, bulk, and for DTLS 1.3
+ * mask; open -- prepare, bulk, for DTLS 1.3 strip, window. */
 BSSL_AMD_EXPORT void BSSL_AMD_set_kernel_timing(int enable);
 BSSL_AMD_EXPORT size_t BSSL_AMD_collect_kernel_times(double *out_ms, size_t max);
 BSSL_AMD_EXPORT double BSSL_AMD_last_kernel_ms(void);

@@ -326,6 +326,160 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_open_tls13_padded_device(BSSL_AMD_TLS_SET *
                                                               const BSSL_AMD_TLS_SET_RECORDS *r,
                                                               void *hip_stream);
 
+/* ---- DTLS 1.2 and 1.3 record protection -----------------------------------
+ *
+ * BSSL_AMD_DTLS_AEAD is one direction of one epoch of one DTLS association:
+ * dtls_seal_record / dtls_open_record (ssl/dtls_record.cc:481-584, 292-425)
+ * for a batch of records.  What differs from TLS: a record's number travels in
+ * its header, so records may arrive reordered, duplicated or forged, and an
+ * opening context keeps the reference's 256-entry anti-replay window
+ * (DTLSReplayBitmap, dtls_record.cc:29-57) -- on the device, so that both
+ * calls only enqueue work on hip_stream, for AES-GCM too.  The state of a
+ * context lives in stream order: issue all calls of one context on one stream,
+ * or order them as if they were.
+ *
+ * The AEAD is the plain one, not the nonce-checking tls12 / tls13 variants:
+ * the context generates its own sequence numbers, so its nonces rise strictly
+ * by construction, and it may start at any `seq` -- the deliberate departure
+ * from the reference that the connection sets document above.
+ *
+ * Wire record i = prefix[i] ++ body ++ suffix[i]; suffix[i] is the 16-byte
+ * tag.  With combined = epoch << 48 | seq:
+ *
+ * DTLS 1.2 (RFC 6347 4.1).  prefix_len 13, or 21 for AES-GCM (the 8-byte
+ * explicit nonce follows the header):
+ *   header  type, be16(0xfefd), be16(epoch), be48(seq), be16(explicit + L + 16)
+ *   body    L bytes
+ *   AD      be64(combined) ++ type ++ fe fd ++ be16(L)
+ *   nonce   AES-GCM: iv4 ++ be64(combined), whose last 8 bytes are the explicit
+ *           nonce written on seal and read from the prefix on open;
+ *           ChaCha20-Poly1305: iv12 XOR (0^4 ++ be64(combined))
+ *
+ * DTLS 1.3 (RFC 9147 4).  prefix_len 5.  The body is the whole fragment,
+ * content ++ type ++ zeros, the layout of the TLS 1.3 padded calls:
+ *   seal    lengths[i] is the content length L; the caller leaves room for
+ *           L + 1 bytes at out + offsets[i] (no padding is added, as in the
+ *           reference); out_lengths[i], when given, receives L + 1
+ *   header  0x2c | (epoch & 3), be16(seq & 0xffff), be16(L + 1 + 16); it is the
+ *           AD, with the sequence bytes in the clear
+ *   nonce   iv12 XOR (0^4 ++ be64(seq)): the sequence number without the epoch
+ *           (dtls_aead_sequence, dtls_record.cc:71-78)
+ *   mask    after the AEAD, header bytes 1..2 are XORed with mask bytes 0..1
+ *           (RFC 9147 4.2.3; ssl/tls13_enc.cc:237-298).  The sample is the
+ *           first 16 bytes of body ++ tag.  AES suites: AES-ECB(sn_key,
+ *           sample); ChaCha20: the first keystream bytes of ChaCha20 with key
+ *           sn_key, block counter le32(sample[0..4)), nonce sample[4..16)
+ *
+ * Seal.  Record i gets sequence number sequence() + i and the context advances
+ * by n.  Returns 0 with nothing launched when sequence() + n - 1 > 2^48 - 1
+ * (HasNext, dtls_record.cc:500-505) or on argument errors: NULL in, out, prefix
+ * or suffix with records present (ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED), the wrong
+ * direction (CIPHER_R_INVALID_OPERATION).  A record fails alone and still
+ * consumes its number -- status 0; body, tag and prefix zeroed; out_lengths[i]
+ * 0 -- when L > 2^14, or in DTLS 1.3 when its type is 0.  record_numbers[i] =
+ * combined is written for every record.
+ *
+ * Open.  Records come in arrival order; lengths[i] is the body length (DTLS
+ * 1.3: the fragment length, the datagram's rest minus 16).  Let (M0, bitmap)
+ * be the window at the point of the stream where the call's work runs.
+ *  1. Parse, per record.  DTLS 1.2: the record fails when its first byte has
+ *     (b & 0xe0) == 0x20, its version is not 0xfefd, its epoch is not the
+ *     context's, its length field is not explicit + lengths[i] + 16 or exceeds
+ *     16704, or lengths[i] > 2^14; types[i] is the header's type byte, s its
+ *     48-bit sequence number.  DTLS 1.3: the first byte is 0 0 1 C S L E E; C
+ *     must be clear and E E equal epoch & 3 (a context is one epoch: the
+ *     caller routes by these bits); S selects a 2- or 1-byte sequence number,
+ *     L says whether a length follows, so the header is the first 2 to 5
+ *     bytes of the 5-byte slot; a stated length must be lengths[i] + 16;
+ *     lengths[i] must be within 1 .. 2^14 + 1.  The mask is computed from the
+ *     sample, the sequence bytes are unmasked and s = reconstruct_seqnum(wire,
+ *     0xff or 0xffff, M0) (dtls_record.cc:92-120): the value congruent to the
+ *     wire bits closest to M0 + 1, the larger one on a tie, within 0 .. 2^48 -
+ *     1.  The AD is the received header with the unmasked sequence bytes.
+ *     The prefix is not modified.
+ *  2. The AEAD opens the parsed records.  DTLS 1.3: the last non-zero byte of
+ *     the fragment is types[i] and its index out_lengths[i]; a fragment of
+ *     zeros fails.
+ *  3. The window, over the records that passed 1 and 2, in index order: record
+ *     i fails if ShouldDiscard(s_i) (older than the maximum - 255, or already
+ *     seen), else Record(s_i).  Records that failed earlier never touch it.
+ * A failed record has status 0, lengths[i] zero bytes of output, out_lengths[i]
+ * 0 and in DTLS 1.3 types[i] 0.  record_numbers[i] = epoch << 48 | s for every
+ * record that passed step 1, else 0.  DTLS 1.2 writes out_lengths[i] =
+ * lengths[i] for an accepted record.  Argument errors as for seal; DTLS 1.3
+ * requires out_lengths.
+ *
+ * One deliberate departure: the reference reconstructs record i against the
+ * window's maximum after records 0..i-1, a batch reconstructs every record
+ * against M0, so that a forged record cannot disturb its neighbours and step 1
+ * stays parallel.  The two agree whenever every genuine record's sequence
+ * number s satisfies -step/2 < s - (M0 + 1) <= step/2 with step 65536 (16-bit)
+ * or 256 (8-bit sequence numbers): callers whose peer sends 8-bit sequence
+ * numbers must keep their batches within that range.  For records in order
+ * that is at most 32768 (or 128) records per DTLS 1.3 open call; a longer run
+ * is issued as several calls back to back on the stream, each of which sees
+ * the window the one before it left.  DTLS 1.2 headers carry all 48 bits and
+ * have no such limit.
+ *
+ * Out of scope: sets of associations, the CBC suites, connection IDs, epoch
+ * switching and the derivation of sn_key, the plaintext epoch 0, splitting a
+ * datagram into records, padding on DTLS 1.3 seal. */
+#define BSSL_AMD_DTLS1_2_VERSION 0xfefd
+#define BSSL_AMD_DTLS1_3_VERSION 0xfefc
+typedef struct bssl_amd_dtls_aead_st BSSL_AMD_DTLS_AEAD;
+
+/* `aead`: EVP_aead_aes_128_gcm(), EVP_aead_aes_256_gcm() or
+ * EVP_aead_chacha20_poly1305().  fixed_iv: 4 bytes for DTLS 1.2 AES-GCM, 12
+ * otherwise.  sn_key: DTLS 1.3, the record-number ("sn") key of
+ * EVP_AEAD_key_length(aead) bytes; DTLS 1.2: NULL, 0.  seq: the first sequence
+ * number of a sealing context (ignored on open).  Checked before any GPU
+ * call: a version that is neither DTLS 1.2 nor 1.3, a NULL aead, key or
+ * fixed_iv, a sn_key that is missing (DTLS 1.3) or given (DTLS 1.2), a DTLS 1.3
+ * epoch of 0 (the plaintext epoch, dtls_record.cc:163-168) or seq > 2^48 - 1 is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; the AES-CTR-HMAC and CBC AEADs
+ * CIPHER_R_CTRL_NOT_IMPLEMENTED; any other AEAD, or a wrong key_len,
+ * fixed_iv_len or sn_key_len, CIPHER_R_UNSUPPORTED_KEY_SIZE. */
+BSSL_AMD_EXPORT BSSL_AMD_DTLS_AEAD *BSSL_AMD_DTLS_AEAD_new(
+    enum evp_aead_direction_t direction, uint16_t version, const EVP_AEAD *aead,
+    const uint8_t *key, size_t key_len, const uint8_t *fixed_iv, size_t fixed_iv_len,
+    const uint8_t *sn_key, size_t sn_key_len, uint16_t epoch, uint64_t seq);
+/* Waits for the device, zeroes the key material and the window on it. */
+BSSL_AMD_EXPORT void BSSL_AMD_DTLS_AEAD_free(BSSL_AMD_DTLS_AEAD *t);
+BSSL_AMD_EXPORT size_t BSSL_AMD_DTLS_AEAD_prefix_len(const BSSL_AMD_DTLS_AEAD *t);
+/* Seal: the sequence number the next record will use. */
+BSSL_AMD_EXPORT uint64_t BSSL_AMD_DTLS_AEAD_sequence(const BSSL_AMD_DTLS_AEAD *t);
+/* The read window, HOST memory; both synchronise hip_stream.  bitmap bit k
+ * (byte k/8, bit k%8) = sequence number max_seq - k seen.  A new open context
+ * has max_seq 0 and an empty bitmap. */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_get_window(BSSL_AMD_DTLS_AEAD *t, uint64_t *max_seq,
+                                                  uint8_t bitmap[32], void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_set_window(BSSL_AMD_DTLS_AEAD *t, uint64_t max_seq,
+                                                  const uint8_t bitmap[32], void *hip_stream);
+
+typedef struct {
+  size_t num_records;
+  const uint8_t *in; /* device */
+  uint8_t *out;      /* device, may equal in */
+  const uint64_t *offsets; /* device, or NULL: i * record_stride */
+  const uint64_t *lengths; /* device, or NULL: record_len */
+  uint64_t record_stride;
+  uint64_t record_len;
+  uint8_t *types; /* as BSSL_AMD_TLS_RECORDS; may be NULL on open */
+  uint8_t type;
+  uint8_t *prefix; /* device, prefix_len bytes per record */
+  uint8_t *suffix; /* device, the 16-byte tag per record */
+  uint8_t *status; /* device, 1 / 0 per record, or NULL */
+  uint64_t *out_lengths;    /* device; DTLS 1.3 open: required, else optional */
+  uint64_t *record_numbers; /* device, optional: epoch << 48 | sequence of record i */
+} BSSL_AMD_DTLS_RECORDS;
+
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_seal_records_device(BSSL_AMD_DTLS_AEAD *t,
+                                                           const BSSL_AMD_DTLS_RECORDS *r,
+                                                           void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_open_records_device(BSSL_AMD_DTLS_AEAD *t,
+                                                           const BSSL_AMD_DTLS_RECORDS *r,
+                                                           void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

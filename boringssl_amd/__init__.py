@@ -98,6 +98,11 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_DTLS_AEAD_sequence", "BSSL_AMD_DTLS_AEAD_get_window",
     "BSSL_AMD_DTLS_AEAD_set_window", "BSSL_AMD_DTLS_AEAD_seal_records_device",
     "BSSL_AMD_DTLS_AEAD_open_records_device",
+    "BSSL_AMD_DTLS_SET_new", "BSSL_AMD_DTLS_SET_free", "BSSL_AMD_DTLS_SET_num_slots",
+    "BSSL_AMD_DTLS_SET_prefix_len", "BSSL_AMD_DTLS_SET_set_slots", "BSSL_AMD_DTLS_SET_clear_slots",
+    "BSSL_AMD_DTLS_SET_sequences", "BSSL_AMD_DTLS_SET_get_windows",
+    "BSSL_AMD_DTLS_SET_set_windows", "BSSL_AMD_DTLS_SET_seal_records_device",
+    "BSSL_AMD_DTLS_SET_open_records_device",
 ]
 TLS13_TAG_LEN = 16  # BSSL_AMD_TLS13_TAG_LEN: the suffix stride of the padded calls
 TLS1_1_VERSION = 0x0302
@@ -160,6 +165,12 @@ class BSSL_AMD_TLS_SET_RECORDS(ctypes.Structure):
     _fields_ = [
         ("records", BSSL_AMD_TLS_RECORDS), ("num_runs", _S), ("run_connection", _P),
         ("run_start", _P),
+    ]
+
+
+class BSSL_AMD_DTLS_SET_RECORDS(ctypes.Structure):
+    _fields_ = [
+        ("records", BSSL_AMD_DTLS_RECORDS), ("num_runs", _S), ("run_slot", _P), ("run_start", _P),
     ]
 
 
@@ -260,6 +271,19 @@ _SIGS = {
                                                     _P]),
     "BSSL_AMD_DTLS_AEAD_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_RECORDS),
                                                     _P]),
+    "BSSL_AMD_DTLS_SET_new": (_P, [_I, ctypes.c_uint16, _P, _S]),
+    "BSSL_AMD_DTLS_SET_free": (None, [_P]),
+    "BSSL_AMD_DTLS_SET_num_slots": (_S, [_P]),
+    "BSSL_AMD_DTLS_SET_prefix_len": (_S, [_P]),
+    "BSSL_AMD_DTLS_SET_set_slots": (_I, [_P, _S, _S, _P, _P, _P, _P, _P, _P]),
+    "BSSL_AMD_DTLS_SET_clear_slots": (_I, [_P, _S, _S, _P]),
+    "BSSL_AMD_DTLS_SET_sequences": (_I, [_P, _S, _S, _P, _P]),
+    "BSSL_AMD_DTLS_SET_get_windows": (_I, [_P, _S, _S, _P, _P, _P]),
+    "BSSL_AMD_DTLS_SET_set_windows": (_I, [_P, _S, _S, _P, _P, _P]),
+    "BSSL_AMD_DTLS_SET_seal_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_SET_RECORDS),
+                                                   _P]),
+    "BSSL_AMD_DTLS_SET_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_SET_RECORDS),
+                                                   _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -740,6 +764,115 @@ def make_tls_set_records(records, run_connection, run_start):
     r.num_runs = 0 if run_connection is None else run_connection.numel()
     r.run_connection, r.run_start = _dptr(run_connection), _dptr(run_start)
     r._refs = (records, getattr(records, "_refs", None), run_connection, run_start)
+    return r
+
+
+class DtlsSet:
+    """BSSL_AMD_DTLS_SET: one direction of many DTLS associations of one version
+    and suite -- per slot the key, fixed IV, sn key, epoch, write sequence
+    number and replay window, resident on the device; one call seals / opens a
+    batch that mixes their records (include/bssl_amd/tls.h)."""
+
+    def __init__(self, direction, version, aead, num_slots):
+        if isinstance(aead, str):
+            aead = EVP_aead(aead)
+        self.h = _lib.BSSL_AMD_DTLS_SET_new(direction, version, aead, num_slots)
+        if not self.h:
+            _fail("BSSL_AMD_DTLS_SET_new")
+
+    @property
+    def num_slots(self):
+        return _lib.BSSL_AMD_DTLS_SET_num_slots(self.h)
+
+    @property
+    def prefix_len(self):
+        return _lib.BSSL_AMD_DTLS_SET_prefix_len(self.h)
+
+    def set_slots(self, first, keys, fixed_ivs, sn_keys=None, epochs=None, seqs=None, stream=None):
+        """(Re)keys slots first.. from sequences of keys, fixed IVs, sn keys
+        (DTLS 1.3, else None), epochs (None: all 1) and (or None: all 0) first
+        write sequence numbers."""
+        n = len(keys)
+        if epochs is None:
+            epochs = [1] * n
+        if (len(fixed_ivs) != n or len(epochs) != n or (seqs is not None and len(seqs) != n) or
+                (sn_keys is not None and len(sn_keys) != n)):
+            raise ValueError("keys, fixed_ivs, sn_keys, epochs and seqs differ in length")
+        kb = b"".join(bytes(k) for k in keys)
+        ib = b"".join(bytes(v) for v in fixed_ivs)
+        nb = None if sn_keys is None else b"".join(bytes(k) for k in sn_keys)
+        eb = (ctypes.c_uint16 * max(n, 1))(*epochs)
+        sb = None if seqs is None else (ctypes.c_uint64 * max(n, 1))(*seqs)
+        if not _lib.BSSL_AMD_DTLS_SET_set_slots(self.h, first, n, kb, ib, nb, eb, sb,
+                                                _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_set_slots")
+
+    def clear_slots(self, first, n, stream=None):
+        if not _lib.BSSL_AMD_DTLS_SET_clear_slots(self.h, first, n, _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_clear_slots")
+
+    def sequences(self, first=0, n=None, stream=None):
+        """A sealing set: the next write sequence numbers of slots
+        first..first+n-1 (synchronises)."""
+        if n is None:
+            n = self.num_slots - first
+        out = (ctypes.c_uint64 * max(n, 1))()
+        if not _lib.BSSL_AMD_DTLS_SET_sequences(self.h, first, n, out, _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_sequences")
+        return [out[i] for i in range(n)]
+
+    def get_windows(self, first=0, n=None, stream=None):
+        """An opening set: [(max_seq, the 32-byte bitmap)] of slots
+        first..first+n-1, as DtlsAead.get_window (synchronises)."""
+        if n is None:
+            n = self.num_slots - first
+        mx = (ctypes.c_uint64 * max(n, 1))()
+        maps = ctypes.create_string_buffer(32 * max(n, 1))
+        if not _lib.BSSL_AMD_DTLS_SET_get_windows(self.h, first, n, mx, maps, _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_get_windows")
+        return [(mx[i], maps.raw[32 * i:32 * i + 32]) for i in range(n)]
+
+    def set_windows(self, first, windows, stream=None):
+        """windows: [(max_seq, 32-byte bitmap)] for slots first.. (synchronises)."""
+        n = len(windows)
+        if any(len(bytes(b)) != 32 for _, b in windows):
+            raise ValueError("a bitmap has 32 bytes")
+        mx = (ctypes.c_uint64 * max(n, 1))(*[m for m, _ in windows])
+        maps = b"".join(bytes(b) for _, b in windows)
+        if not _lib.BSSL_AMD_DTLS_SET_set_windows(self.h, first, n, mx, maps, _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_set_windows")
+
+    def seal_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_DTLS_SET_seal_records_device(self.h, ctypes.byref(recs),
+                                                          _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_seal_records_device")
+
+    def open_records_device(self, recs, stream=None):
+        if not _lib.BSSL_AMD_DTLS_SET_open_records_device(self.h, ctypes.byref(recs),
+                                                          _stream_ptr(stream)):
+            _fail("BSSL_AMD_DTLS_SET_open_records_device")
+
+    def close(self):
+        if self.h:
+            _lib.BSSL_AMD_DTLS_SET_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
+def make_dtls_set_records(records, run_slot, run_start):
+    """BSSL_AMD_DTLS_SET_RECORDS from a make_dtls_records() structure and the
+    device tensors run_slot (int32 / uint32, num_runs entries) and run_start
+    (int64, num_runs + 1 entries); keeps references."""
+    r = BSSL_AMD_DTLS_SET_RECORDS()
+    r.records = records
+    r.num_runs = 0 if run_slot is None else run_slot.numel()
+    r.run_slot, r.run_start = _dptr(run_slot), _dptr(run_start)
+    r._refs = (records, getattr(records, "_refs", None), run_slot, run_start)
     return r
 
 

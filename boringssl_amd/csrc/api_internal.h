@@ -82,6 +82,21 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
 // launch order with the bulk kernels' pairs; null otherwise.  The pointer holds
 // until the next pair is taken.
 const KernelEvents *kernel_timing_pair();
+// Brackets the launches of one step of a call with such a pair (dtls_api.cc,
+// dtls_set_api.cc).
+struct Timed {
+  const KernelEvents *ev;
+  hipStream_t s;
+  explicit Timed(hipStream_t stream) : ev(kernel_timing_pair()), s(stream) {
+    if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->start), s);
+  }
+  // (Before the next pair is taken: the pointer holds until then.)
+  void stop() {
+    if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
+    ev = nullptr;
+  }
+};
+
 // kAeadTlsCbc: the MAC size (e_tls.cc:105-116).
 size_t tls_cbc_mac_len(const EVP_AEAD *aead);
 uint64_t load_be64(const uint8_t *p);

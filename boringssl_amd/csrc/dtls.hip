@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void dtls_prepare_kernel(DtlsPrepare p) {
   }
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  dtls_prepare_record<MASK>(p, i, p.seq + i, TlsIv::from_bytes(p.fixed_iv), p.state->max_seq,
+  dtls_prepare_record<MASK>(p, i, p.epoch, p.seq + i, TlsIv::from_bytes(p.fixed_iv), p.state->max_seq,
                             p.state->sn, L);
 }
 

@@ -77,20 +77,6 @@ struct DtlsScratch {
   DtlsScratch &operator=(const DtlsScratch &) = delete;
 };
 
-// Brackets the launches of one step with a timing pair (api_internal.h).
-struct Timed {
-  const KernelEvents *ev;
-  hipStream_t s;
-  explicit Timed(hipStream_t stream) : ev(kernel_timing_pair()), s(stream) {
-    if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->start), s);
-  }
-  // (Before the next pair is taken: the pointer holds until then.)
-  void stop() {
-    if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-    ev = nullptr;
-  }
-};
-
 bool present(const void *p) {
   if (p) return true;
   PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);

@@ -1,9 +1,9 @@
 // dtls_prepare.h -- the per-record body of the DTLS record layer's prepare
 // step (dtls.hip: dtls_prepare_kernel, one direction of one epoch), one
 // __device__ function as tls_prepare.h has for TLS, so that a prepare kernel
-// over many associations can share it: the differences are in what the caller
-// passes (the sequence number, the fixed IV, the window's maximum, the
-// record-number key).
+// over many associations (dtls_set.hip) shares it: the differences are in what
+// the caller passes (the epoch, the sequence number, the fixed IV, the window's
+// maximum, the record-number key).
 //
 // Reference (one record per call): dtls_seal_record / dtls_open_record
 // (ssl/dtls_record.cc:481-584, 292-425), SSLAEADContext (ssl/ssl_aead_ctx.cc:
@@ -37,8 +37,9 @@ __device__ __forceinline__ uint4 dtls_sample(const uint8_t *frag, uint64_t frag_
 }
 
 // Mask bytes 0 (bits 0..7) and 1 (bits 8..15) of a sample.  sn: the
-// record-number key as DtlsState holds it (wave-uniform); L: the workgroup's
-// T-table (AES), unused otherwise.
+// record-number key as DtlsState holds it -- wave-uniform for one association,
+// the lane's own for a set (AES: its LDS slot, lane_frame.h); L: the
+// workgroup's T-table (AES), unused otherwise.
 template <int MASK, class LDS>
 __device__ __forceinline__ uint32_t dtls_mask16(uint4 sample, const uint32_t *sn, const LDS &L) {
   if constexpr (dtls_mask_is_aes(MASK)) {
@@ -84,10 +85,10 @@ __device__ __forceinline__ void dtls_xor_nonce(uint8_t *nonce, const TlsIv &iv, 
 // Seal: record i with sequence number seq.  valid[i] comes from the TLS 1.3
 // pre-pass (tls_pad.hip) in DTLS 1.3, whose lengths are the fragment lengths;
 // in DTLS 1.2 it is written here.
-__device__ __forceinline__ void dtls_seal_record(const DtlsPrepare &p, uint64_t i, uint64_t seq,
-                                                 const TlsIv &iv) {
+__device__ __forceinline__ void dtls_seal_record(const DtlsPrepare &p, uint64_t i, uint32_t epoch,
+                                                 uint64_t seq, const TlsIv &iv) {
   const uint64_t len = p.lengths ? p.lengths[i] : p.record_len;
-  const uint64_t combined = ((uint64_t)p.epoch << 48) | seq;
+  const uint64_t combined = ((uint64_t)epoch << 48) | seq;
   uint8_t *pre = p.prefix + p.prefix_len * i;
   uint8_t *nonce = p.nonces + 12 * i;
   uint8_t *ad = p.ad + p.ad_stride * i;
@@ -99,7 +100,7 @@ __device__ __forceinline__ void dtls_seal_record(const DtlsPrepare &p, uint64_t 
     // the sequence number alone (dtls_aead_sequence, :71-78).
     ok = p.valid[i] != 0;
     const uint64_t ctlen = len + 16;
-    const uint8_t hdr[5] = {(uint8_t)(0x2c | (p.epoch & 3)), (uint8_t)(seq >> 8), (uint8_t)seq,
+    const uint8_t hdr[5] = {(uint8_t)(0x2c | (epoch & 3)), (uint8_t)(seq >> 8), (uint8_t)seq,
                             (uint8_t)(ctlen >> 8), (uint8_t)ctlen};
     for (int k = 0; k < 5; k++) {
       pre[k] = ok ? hdr[k] : 0;
@@ -144,9 +145,9 @@ __device__ __forceinline__ void dtls_seal_record(const DtlsPrepare &p, uint64_t 
 // dtls_mask16.  Writes valid[i], seqs[i] and record_numbers[i] for every
 // record.
 template <int MASK, class LDS>
-__device__ __forceinline__ void dtls_open_record(const DtlsPrepare &p, uint64_t i, const TlsIv &iv,
-                                                 uint64_t max_seq, const uint32_t *sn,
-                                                 const LDS &L) {
+__device__ __forceinline__ void dtls_open_record(const DtlsPrepare &p, uint64_t i, uint32_t epoch,
+                                                 const TlsIv &iv, uint64_t max_seq,
+                                                 const uint32_t *sn, const LDS &L) {
   const uint64_t len = p.lengths ? p.lengths[i] : p.record_len;
   const uint8_t *pre = p.prefix + p.prefix_len * i;
   uint8_t *nonce = p.nonces + 12 * i;
@@ -160,7 +161,7 @@ __device__ __forceinline__ void dtls_open_record(const DtlsPrepare &p, uint64_t 
     const uint32_t hdr_len = 1 + seq_len + 2 * has_len;
     const uint32_t w0 = pre[1], w1 = pre[2], w2 = pre[3], w3 = pre[4];
     const uint64_t stated = seq_len == 2 ? (w2 << 8) | w3 : (w1 << 8) | w2;
-    ok = (b0 & 0xe0) == 0x20 && (b0 & 0x10) == 0 && (b0 & 3) == (uint32_t)(p.epoch & 3) &&
+    ok = (b0 & 0xe0) == 0x20 && (b0 & 0x10) == 0 && (b0 & 3) == (epoch & 3) &&
          len >= 1 && len <= kTlsMaxPlainLen + 1 &&
          (!has_len || (stated == len + 16 && stated <= kTlsMaxEncryptedLen));
     uint32_t m = 0;
@@ -184,13 +185,13 @@ __device__ __forceinline__ void dtls_open_record(const DtlsPrepare &p, uint64_t 
     const uint32_t explicit_len = p.prefix_len - 13;
     const uint32_t type = pre[0];
     const uint32_t version = ((uint32_t)pre[1] << 8) | pre[2];
-    const uint32_t epoch = ((uint32_t)pre[3] << 8) | pre[4];
+    const uint32_t hdr_epoch = ((uint32_t)pre[3] << 8) | pre[4];
     for (int k = 0; k < 6; k++) s = (s << 8) | pre[5 + k];
     const uint64_t stated = ((uint64_t)pre[11] << 8) | pre[12];
-    ok = (type & 0xe0) != 0x20 && version == 0xfefd && epoch == p.epoch &&
+    ok = (type & 0xe0) != 0x20 && version == 0xfefd && hdr_epoch == epoch &&
          len <= kTlsMaxPlainLen && stated == explicit_len + len + 16 &&
          stated <= kTlsMaxEncryptedLen;
-    const uint64_t combined = ((uint64_t)p.epoch << 48) | s;
+    const uint64_t combined = ((uint64_t)epoch << 48) | s;
     if (p.types_out) p.types_out[i] = (uint8_t)type;
     if (p.xor_nonce) {
       dtls_xor_nonce(nonce, iv, combined);
@@ -207,18 +208,20 @@ __device__ __forceinline__ void dtls_open_record(const DtlsPrepare &p, uint64_t 
   }
   p.valid[i] = ok ? 1 : 0;
   p.seqs[i] = s;
-  if (p.record_numbers) p.record_numbers[i] = ok ? ((uint64_t)p.epoch << 48) | s : 0;
+  if (p.record_numbers) p.record_numbers[i] = ok ? ((uint64_t)epoch << 48) | s : 0;
 }
 
-// Record i of a batch: seq is read on seal, max_seq / sn / L on open.
+// Record i of a batch in epoch `epoch` (one association: DtlsPrepare::epoch; a
+// set: the slot's): seq is read on seal, max_seq / sn / L on open.
 template <int MASK, class LDS>
-__device__ __forceinline__ void dtls_prepare_record(const DtlsPrepare &p, uint64_t i, uint64_t seq,
-                                                    const TlsIv &iv, uint64_t max_seq,
-                                                    const uint32_t *sn, const LDS &L) {
+__device__ __forceinline__ void dtls_prepare_record(const DtlsPrepare &p, uint64_t i,
+                                                    uint32_t epoch, uint64_t seq, const TlsIv &iv,
+                                                    uint64_t max_seq, const uint32_t *sn,
+                                                    const LDS &L) {
   if (p.open)
-    dtls_open_record<MASK>(p, i, iv, max_seq, sn, L);
+    dtls_open_record<MASK>(p, i, epoch, iv, max_seq, sn, L);
   else
-    dtls_seal_record(p, i, seq, iv);
+    dtls_seal_record(p, i, epoch, seq, iv);
 }
 
 }  // namespace

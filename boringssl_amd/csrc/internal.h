@@ -523,6 +523,74 @@ struct DtlsWindow {
   DtlsState *state;
 };
 int launch_dtls_window(const DtlsWindow &p, void *stream);
+// DTLS association sets (dtls_set.hip; BSSL_AMD_DTLS_SET): what a slot -- one
+// direction of one epoch of one association -- keeps on the device.  All zero:
+// unset.
+struct alignas(16) DtlsSetSlot {
+  // Seal: the next write sequence number; 2^48: exhausted.
+  uint64_t seq;
+  // Open: the read window, as DtlsState has it.
+  uint64_t max_seq;
+  uint64_t bitmap[4];
+  // The fixed IV as TlsSetConn has it (DTLS 1.2 AES-GCM: 4 bytes, then zeros).
+  uint64_t iv_lo;
+  uint32_t iv_hi;
+  uint32_t live;   // 1: keys, IV and epoch installed
+  // Within one call: ~j of the lowest non-empty run j that names this slot
+  // (atomicMax; 0: none).  0 between calls.
+  uint32_t claim;
+  uint32_t epoch;
+  uint64_t pad;
+  // DTLS 1.3: the record-number key, as DtlsState::sn.
+  uint32_t sn[60];
+};
+static_assert(sizeof(DtlsSetSlot) == 80 + 240, "layout");
+// One batch over many slots: records [run_start[j], run_start[j+1]) belong to
+// slot run_slot[j].  rec.fixed_iv, rec.epoch, rec.seq and rec.state are unused
+// (they come from the slot); rec.valid, rec.seqs (open) and key_index are
+// written for every record.  Scratch, by the launchers' order of use:
+//   flag      one word, zero: set when run_start is malformed
+//   run_of    per record: j + 1 of the run whose slot the record was prepared
+//             with, 0 for a record that has none
+//   run_won   per run: c + 1 when run j won the live slot c in a well-formed
+//             batch, else 0 (the advance kernel, for the window)
+struct DtlsSetPrepare {
+  DtlsPrepare rec;
+  DtlsSetSlot *slots;
+  uint32_t num_slots;
+  uint64_t num_runs;
+  const uint32_t *run_slot;
+  const uint64_t *run_start;  // num_runs + 1 entries
+  uint32_t *key_index;
+  uint32_t *flag;
+  uint32_t *run_of;
+  uint32_t *run_won;
+};
+// Three launches in stream order: the runs claim their slots and check
+// run_start, every record is prepared from its slot (or failed), the runs that
+// won advance their slots' write sequence numbers (seal) and clear the claims.
+int launch_dtls_set_prepare(const DtlsSetPrepare &p, int mask, void *stream);
+// After a DTLS 1.3 seal: DtlsMaskSeal with record i's key in slots[key_index[i]]
+// (m.state is unused).
+int launch_dtls_set_mask(const DtlsMaskSeal &m, const DtlsSetSlot *slots, uint32_t num_slots,
+                         const uint32_t *key_index, int mask, void *stream);
+// Step 3 of an open over a set: one window per slot, over each run's records
+// with status[i] != 0 in index order (w.state, w.old and w.block_max are
+// unused; w.table holds table_slots uint32 record indices, all ones).  run_max:
+// one zeroed uint64 per run; old: 6 uint64 per run; block_r / block_s: one
+// entry per 256 records.
+struct DtlsSetWindow {
+  DtlsWindow w;
+  DtlsSetSlot *slots;
+  uint64_t num_runs;
+  const uint32_t *run_of;
+  const uint32_t *run_won;
+  uint64_t *run_max;
+  uint64_t *old;
+  uint32_t *block_r;
+  uint64_t *block_s;
+};
+int launch_dtls_set_window(const DtlsSetWindow &p, void *stream);
 // Record-layer limits (include/openssl/ssl3.h of the reference).
 constexpr uint64_t kTlsMaxPlainLen = 16384;
 constexpr uint64_t kTlsMaxEncryptedLen = 16384 + 320;

@@ -421,9 +421,10 @@ BSSL_AMD_EXPORT int BSSL_AMD_TLS_SET_open_tls13_padded_device(BSSL_AMD_TLS_SET *
  * the window the one before it left.  DTLS 1.2 headers carry all 48 bits and
  * have no such limit.
  *
- * Out of scope: sets of associations, the CBC suites, connection IDs, epoch
- * switching and the derivation of sn_key, the plaintext epoch 0, splitting a
- * datagram into records, padding on DTLS 1.3 seal. */
+ * Out of scope: the CBC suites, connection IDs, epoch switching and the
+ * derivation of sn_key, the plaintext epoch 0, splitting a datagram into
+ * records, padding on DTLS 1.3 seal.  (Many associations in one batch:
+ * BSSL_AMD_DTLS_SET below.) */
 #define BSSL_AMD_DTLS1_2_VERSION 0xfefd
 #define BSSL_AMD_DTLS1_3_VERSION 0xfefc
 typedef struct bssl_amd_dtls_aead_st BSSL_AMD_DTLS_AEAD;
@@ -479,6 +480,135 @@ BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_seal_records_device(BSSL_AMD_DTLS_AEAD *t
 BSSL_AMD_EXPORT int BSSL_AMD_DTLS_AEAD_open_records_device(BSSL_AMD_DTLS_AEAD *t,
                                                            const BSSL_AMD_DTLS_RECORDS *r,
                                                            void *hip_stream);
+
+/* ---- DTLS association sets: one record batch across many associations ------
+ *
+ * BSSL_AMD_DTLS_SET is one direction of up to num_slots slots of ONE version
+ * (DTLS 1.2 or 1.3) and ONE AEAD suite.  A slot is what a BSSL_AMD_DTLS_AEAD
+ * is -- one direction of one epoch of one association -- with all of its state
+ * on the device: key, fixed IV, sn key (DTLS 1.3), epoch, the next write
+ * sequence number S[c] (seal), the window's maximum and 256-bit map (open).
+ * The caller maps (association, epoch) to slots and routes records by their
+ * epoch bits, as for one association.  One call protects a batch that mixes
+ * the records of many slots and only enqueues work on hip_stream: seal and
+ * open never synchronise it, not for AES-GCM either.  The state of a set lives
+ * in stream order: issue all calls of one set on one stream, or order them as
+ * if they were.
+ *
+ * Records [run_start[j], run_start[j+1]) of a batch belong to slot
+ * c = run_slot[j]; the record layout is BSSL_AMD_DTLS_RECORDS's.
+ *
+ * Equivalence.  For a well-formed batch, everything written for the records
+ * of run j -- prefix, body, tag, status, types, out_lengths, record_numbers --
+ * and the slot's state afterwards are byte for byte what
+ * BSSL_AMD_DTLS_AEAD_new(direction, version, aead, key_c, iv_c, sn_c, epoch_c,
+ * S[c]), on open with its window set to the slot's, produces for those records
+ * in order in one call.  That includes the batch-start reconstruction rule:
+ * every DTLS 1.3 record of a run is reconstructed against ITS SLOT's maximum
+ * at the point of the stream where the call's work runs, so the 32768 / 128
+ * in-order bound holds per slot per call, not per call.
+ *
+ * Seal.  Record i of run j gets the sequence number S[c] + (i - run_start[j]),
+ * and S[c] advances by the run's record count, on the device.  A record whose
+ * number would pass 2^48 - 1 fails alone and gets no number, and S[c]
+ * saturates at 2^48 (exhausted): the one-association call fails as a whole
+ * there, a set does not let one exhausted association fail the others.
+ *
+ * Open.  The replay windows are per slot: two runs that carry the same
+ * sequence numbers are unrelated, a number in one run never moves another
+ * run's maximum, and only the records that authenticated touch their slot's
+ * window, in index order within their run.
+ *
+ * Records that fail alone, besides those that fail in the one-association
+ * layer -- status 0; body and tag zeroed (a DTLS 1.3 seal: all L + 1 bytes of
+ * the fragment); on seal the prefix zeroed; out_lengths[i], types[i] (open)
+ * and record_numbers[i] 0; no sequence number consumed and the slot's window
+ * untouched by them:
+ *   - run_slot[j] is out of range, or the slot is unset or cleared;
+ *   - the slot already has an earlier non-empty run in this call: the lowest j
+ *     wins, and the slot's counter or window moves by the winning run only.
+ *
+ * Malformed run_start.  Deliberately stricter than the TLS set: when
+ * run_start is not non-decreasing, or run_start[0] != 0, or
+ * run_start[num_runs] != num_records, every record of the call fails as above
+ * and no slot's sequence number or window changes.  Nothing outside the
+ * batch's arrays is read or written.  (The check runs on the device: the call
+ * itself still returns 1.)
+ *
+ * Out of scope: the CBC suites, connection IDs, the plaintext epoch 0, mixed
+ * suites or versions in one set, more than one run per slot per call, the
+ * derivation of sn keys, splitting a datagram into records. */
+typedef struct bssl_amd_dtls_set_st BSSL_AMD_DTLS_SET;
+
+/* The version / aead rules and codes of BSSL_AMD_DTLS_AEAD_new; num_slots 0 or
+ * above 2^32 - 2 is ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED.  All checks come before
+ * any GPU call.  All slots start unset. */
+BSSL_AMD_EXPORT BSSL_AMD_DTLS_SET *BSSL_AMD_DTLS_SET_new(enum evp_aead_direction_t direction,
+                                                         uint16_t version, const EVP_AEAD *aead,
+                                                         size_t num_slots);
+/* Waits for the device, zeroes the key material and the windows on it and
+ * frees it. */
+BSSL_AMD_EXPORT void BSSL_AMD_DTLS_SET_free(BSSL_AMD_DTLS_SET *s);
+BSSL_AMD_EXPORT size_t BSSL_AMD_DTLS_SET_num_slots(const BSSL_AMD_DTLS_SET *s);
+/* 13 / 21 / 5, as BSSL_AMD_DTLS_AEAD_prefix_len. */
+BSSL_AMD_EXPORT size_t BSSL_AMD_DTLS_SET_prefix_len(const BSSL_AMD_DTLS_SET *s);
+
+/* (Re)key slots first .. first+n-1 from HOST arrays: n keys, n fixed IVs (4
+ * bytes each for DTLS 1.2 AES-GCM, 12 otherwise), n sn keys of the key's
+ * length (DTLS 1.3; NULL for DTLS 1.2), n epochs, n first write sequence
+ * numbers (NULL: all 0; not used by an opening set).  An installed opening
+ * slot has an empty window at 0.  Ordered on hip_stream like
+ * BSSL_AMD_TLS_SET_set_connections; the host copies of the key material are
+ * zeroed before the call returns.  Checked before any GPU call, all
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED: a slot range outside the set, NULL keys,
+ * fixed_ivs or epochs, sn_keys missing (DTLS 1.3) or given (DTLS 1.2), a DTLS
+ * 1.3 epoch of 0, a sequence number above 2^48 - 1. */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_set_slots(BSSL_AMD_DTLS_SET *s, size_t first, size_t n,
+                                                const uint8_t *keys, const uint8_t *fixed_ivs,
+                                                const uint8_t *sn_keys, const uint16_t *epochs,
+                                                const uint64_t *seqs, void *hip_stream);
+/* Unset slots: key material, counter and window zeroed on the device, in
+ * stream order; their records then fail.  Only enqueues work. */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_clear_slots(BSSL_AMD_DTLS_SET *s, size_t first, size_t n,
+                                                  void *hip_stream);
+/* A sealing set: the next write sequence numbers of slots first..first+n-1 to
+ * HOST memory (0 for an unset slot, 2^48 for an exhausted one); synchronises
+ * hip_stream.  An opening set: CIPHER_R_INVALID_OPERATION. */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_sequences(BSSL_AMD_DTLS_SET *s, size_t first, size_t n,
+                                                uint64_t *out, void *hip_stream);
+/* An opening set: the read windows of slots first..first+n-1, HOST arrays of n
+ * maxima and n 32-byte maps in the bit order of BSSL_AMD_DTLS_AEAD_get_window;
+ * both synchronise hip_stream.  With them a live association moves onto the
+ * set.  A maximum above 2^48 - 1 is ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; a
+ * sealing set CIPHER_R_INVALID_OPERATION. */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_get_windows(BSSL_AMD_DTLS_SET *s, size_t first, size_t n,
+                                                  uint64_t *max_seqs, uint8_t *bitmaps,
+                                                  void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_set_windows(BSSL_AMD_DTLS_SET *s, size_t first, size_t n,
+                                                  const uint64_t *max_seqs,
+                                                  const uint8_t *bitmaps, void *hip_stream);
+
+typedef struct {
+  BSSL_AMD_DTLS_RECORDS records; /* layout exactly as for one association;
+                                    at most 2^32 - 2 records */
+  size_t num_runs;               /* at most 2^32 - 2 */
+  const uint32_t *run_slot;      /* device, num_runs entries */
+  const uint64_t *run_start; /* device, num_runs + 1 entries, non-decreasing,
+                                run_start[0] = 0, run_start[num_runs] = num_records */
+} BSSL_AMD_DTLS_SET_RECORDS;
+
+/* Seal (open) the batch; see above.  Returns 0 with nothing launched and an
+ * error queued for argument errors: NULL pointers as for one association,
+ * num_runs == 0 with num_records != 0, missing run arrays, a count above
+ * 2^32 - 2, DTLS 1.3 open without out_lengths (all
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED), the wrong direction
+ * (CIPHER_R_INVALID_OPERATION). */
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_seal_records_device(BSSL_AMD_DTLS_SET *s,
+                                                          const BSSL_AMD_DTLS_SET_RECORDS *r,
+                                                          void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_open_records_device(BSSL_AMD_DTLS_SET *s,
+                                                          const BSSL_AMD_DTLS_SET_RECORDS *r,
+                                                          void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,9 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_DTLS_SET_sequences", "BSSL_AMD_DTLS_SET_get_windows",
     "BSSL_AMD_DTLS_SET_set_windows", "BSSL_AMD_DTLS_SET_seal_records_device",
     "BSSL_AMD_DTLS_SET_open_records_device",
+    "BSSL_AMD_QUIC_AEAD_new", "BSSL_AMD_QUIC_AEAD_free", "BSSL_AMD_QUIC_AEAD_next_packet_number",
+    "BSSL_AMD_QUIC_AEAD_get_expected", "BSSL_AMD_QUIC_AEAD_set_expected",
+    "BSSL_AMD_QUIC_AEAD_seal_packets_device", "BSSL_AMD_QUIC_AEAD_open_packets_device",
 ]
 TLS13_TAG_LEN = 16  # BSSL_AMD_TLS13_TAG_LEN: the suffix stride of the padded calls
 TLS1_1_VERSION = 0x0302
@@ -171,6 +174,15 @@ class BSSL_AMD_TLS_SET_RECORDS(ctypes.Structure):
 class BSSL_AMD_DTLS_SET_RECORDS(ctypes.Structure):
     _fields_ = [
         ("records", BSSL_AMD_DTLS_RECORDS), ("num_runs", _S), ("run_slot", _P), ("run_start", _P),
+    ]
+
+
+class BSSL_AMD_QUIC_PACKETS(ctypes.Structure):
+    _fields_ = [
+        ("num_packets", _S), ("in_", _P), ("out", _P), ("offsets", _P), ("lengths", _P),
+        ("packet_stride", ctypes.c_uint64), ("packet_len", ctypes.c_uint64), ("pn_offsets", _P),
+        ("pn_offset", ctypes.c_uint32), ("pn_lengths", _P), ("pn_length", ctypes.c_uint8),
+        ("status", _P), ("out_lengths", _P), ("header_lengths", _P), ("packet_numbers", _P),
     ]
 
 
@@ -284,6 +296,15 @@ _SIGS = {
                                                    _P]),
     "BSSL_AMD_DTLS_SET_open_records_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_DTLS_SET_RECORDS),
                                                    _P]),
+    "BSSL_AMD_QUIC_AEAD_new": (_P, [_I, _P, _P, _S, _P, _S, _P, _S, ctypes.c_uint64]),
+    "BSSL_AMD_QUIC_AEAD_free": (None, [_P]),
+    "BSSL_AMD_QUIC_AEAD_next_packet_number": (ctypes.c_uint64, [_P]),
+    "BSSL_AMD_QUIC_AEAD_get_expected": (_I, [_P, ctypes.POINTER(ctypes.c_uint64), _P]),
+    "BSSL_AMD_QUIC_AEAD_set_expected": (_I, [_P, ctypes.c_uint64, _P]),
+    "BSSL_AMD_QUIC_AEAD_seal_packets_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_QUIC_PACKETS),
+                                                    _P]),
+    "BSSL_AMD_QUIC_AEAD_open_packets_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_QUIC_PACKETS),
+                                                    _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -668,6 +689,76 @@ def make_dtls_records(num_records, inp, out, prefix, suffix, *, offsets=None, le
     r.out_lengths, r.record_numbers = _dptr(out_lengths), _dptr(record_numbers)
     r._refs = (inp, out, offsets, lengths, types, prefix, suffix, status, out_lengths,
                record_numbers)
+    return r
+
+
+class QuicAead:
+    """BSSL_AMD_QUIC_AEAD: one direction of one key generation of a QUIC
+    connection sealing / opening device batches of packets, header protection
+    included; an opening context keeps `expected` on the device (tls.h)."""
+
+    def __init__(self, direction, aead, key, iv, hp_key, next_pn=0):
+        if isinstance(aead, str):
+            aead = EVP_aead(aead)
+        key, iv, hp_key = bytes(key), bytes(iv), bytes(hp_key)
+        self.h = _lib.BSSL_AMD_QUIC_AEAD_new(direction, aead, key, len(key), iv, len(iv), hp_key,
+                                             len(hp_key), next_pn)
+        if not self.h:
+            _fail("BSSL_AMD_QUIC_AEAD_new")
+
+    @property
+    def next_packet_number(self):
+        return _lib.BSSL_AMD_QUIC_AEAD_next_packet_number(self.h)
+
+    def get_expected(self, stream=None):
+        """The largest authenticated packet number + 1, or 0 (synchronises)."""
+        expected = ctypes.c_uint64(0)
+        if not _lib.BSSL_AMD_QUIC_AEAD_get_expected(self.h, ctypes.byref(expected),
+                                                    _stream_ptr(stream)):
+            _fail("BSSL_AMD_QUIC_AEAD_get_expected")
+        return expected.value
+
+    def set_expected(self, expected, stream=None):
+        if not _lib.BSSL_AMD_QUIC_AEAD_set_expected(self.h, expected, _stream_ptr(stream)):
+            _fail("BSSL_AMD_QUIC_AEAD_set_expected")
+
+    def seal_packets_device(self, packets, stream=None):
+        if not _lib.BSSL_AMD_QUIC_AEAD_seal_packets_device(self.h, ctypes.byref(packets),
+                                                           _stream_ptr(stream)):
+            _fail("BSSL_AMD_QUIC_AEAD_seal_packets_device")
+
+    def open_packets_device(self, packets, stream=None):
+        if not _lib.BSSL_AMD_QUIC_AEAD_open_packets_device(self.h, ctypes.byref(packets),
+                                                           _stream_ptr(stream)):
+            _fail("BSSL_AMD_QUIC_AEAD_open_packets_device")
+
+    def close(self):
+        if self.h:
+            _lib.BSSL_AMD_QUIC_AEAD_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass
+
+
+def make_quic_packets(num_packets, inp, out, *, offsets=None, lengths=None, packet_stride=0,
+                      packet_len=0, pn_offsets=None, pn_offset=0, pn_lengths=None, pn_length=0,
+                      status=None, out_lengths=None, header_lengths=None, packet_numbers=None):
+    """BSSL_AMD_QUIC_PACKETS from torch device tensors (keeps references)."""
+    r = BSSL_AMD_QUIC_PACKETS()
+    r.num_packets = num_packets
+    r.in_, r.out = _dptr(inp), _dptr(out)
+    r.offsets, r.lengths = _dptr(offsets), _dptr(lengths)
+    r.packet_stride, r.packet_len = packet_stride, packet_len
+    r.pn_offsets, r.pn_offset = _dptr(pn_offsets), pn_offset
+    r.pn_lengths, r.pn_length = _dptr(pn_lengths), pn_length
+    r.status, r.out_lengths = _dptr(status), _dptr(out_lengths)
+    r.header_lengths, r.packet_numbers = _dptr(header_lengths), _dptr(packet_numbers)
+    r._refs = (inp, out, offsets, lengths, pn_offsets, pn_lengths, status, out_lengths,
+               header_lengths, packet_numbers)
     return r
 
 

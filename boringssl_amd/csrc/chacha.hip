@@ -1467,7 +1467,8 @@ void launch_dir(const ChaChaKeyDev *keys, const BatchDesc &b, bool open, hipStre
 // (one dwordx4 per 16 bytes at any address): 1350-byte records at a
 // 1351-byte stride 994 against 158 GiB/s through the aligned kernels' byte
 // path (profiles/r03/s16/).  Ragged batches keep the aligned kernels (an
-// unaligned record there takes the byte path).
+// unaligned record there takes the byte path) unless the caller says that
+// its records start anywhere (BatchDesc::any_align: QUIC packet bodies).
 bool unaligned_uniform(const BatchDesc &b) {
   return !b.offsets &&
          ((reinterpret_cast<uintptr_t>(b.in) | reinterpret_cast<uintptr_t>(b.out) |
@@ -1520,7 +1521,7 @@ int launch_chacha(const ChaChaKeyDev *keys, const BatchDesc &b, bool open, bool 
   if (b.iovecs) {  // iovec records walked in place (never with extra bytes)
     xchacha ? launch_dir<false, true, true, false>(keys, bo, open, s)
             : launch_dir<false, false, true, false>(keys, bo, open, s);
-  } else if (!xt && unaligned_uniform(b)) {
+  } else if (!xt && (unaligned_uniform(b) || b.any_align)) {
     xchacha ? launch_dir<false, true, false, false, true>(keys, bo, open, s)
             : launch_dir<false, false, false, false, true>(keys, bo, open, s);
   } else if (xchacha) {

@@ -36,17 +36,20 @@ __device__ __forceinline__ uint4 dtls_sample(const uint8_t *frag, uint64_t frag_
   return make_uint4(a.x | s.x, a.y | s.y, a.z | s.z, a.w | s.w);
 }
 
-// Mask bytes 0 (bits 0..7) and 1 (bits 8..15) of a sample.  sn: the
+// The first four mask bytes of a sample (byte k: bits 8k..8k+7) and, in *next,
+// the four after them (QUIC's mask has five, quic_prepare.h).  sn: the
 // record-number key as DtlsState holds it -- wave-uniform for one association,
 // the lane's own for a set (AES: its LDS slot, lane_frame.h); L: the
 // workgroup's T-table (AES), unused otherwise.
 template <int MASK, class LDS>
-__device__ __forceinline__ uint32_t dtls_mask16(uint4 sample, const uint32_t *sn, const LDS &L) {
+__device__ __forceinline__ uint32_t dtls_mask_words(uint4 sample, const uint32_t *sn, const LDS &L,
+                                                    uint32_t *next) {
   if constexpr (dtls_mask_is_aes(MASK)) {
     // AES-ECB(sn_key, sample) (tls13_enc.cc:243-251).
     uint4 s[1] = {sample};
     aes_n<MASK == kDtlsMaskAes128 ? 10 : 14, 1>(s, sn, L);
-    return s[0].x & 0xffffu;
+    *next = s[0].y;
+    return s[0].x;
   } else if constexpr (MASK == kDtlsMaskChaCha) {
     // The first keystream bytes of ChaCha20 (RFC 8439 2.3) with block counter
     // le32(sample[0..4)) and nonce sample[4..16) (tls13_enc.cc:279-293).
@@ -58,10 +61,19 @@ __device__ __forceinline__ uint32_t dtls_mask16(uint4 sample, const uint32_t *sn
     in[15] = sample.w;
     uint32_t head[4];
     chacha20_block_head(in, head);
-    return head[0] & 0xffffu;
+    *next = head[1];
+    return head[0];
   } else {
+    *next = 0;
     return 0;
   }
+}
+
+// Mask bytes 0 (bits 0..7) and 1 (bits 8..15) of a sample.
+template <int MASK, class LDS>
+__device__ __forceinline__ uint32_t dtls_mask16(uint4 sample, const uint32_t *sn, const LDS &L) {
+  uint32_t next;
+  return dtls_mask_words<MASK>(sample, sn, L, &next) & 0xffffu;
 }
 
 // reconstruct_seqnum (dtls_record.cc:92-120): the value congruent to `wire`

@@ -196,6 +196,11 @@ struct BatchDesc {
   // one with a bad MAC (tls_record.cc:204-209, SSL3_RT_MAX_PLAIN_LENGTH).  Set
   // by the TLS record layer only; 0: no limit.
   uint64_t max_plain_len;
+  // Set by the QUIC layer only (quic_api.cc): the records of this ragged batch
+  // start wherever a header of any length ends, so hardly any is 16-byte
+  // aligned.  ChaCha20-Poly1305 then takes its any-alignment kernels, which
+  // launch_chacha otherwise picks for unaligned uniform batches only.
+  uint32_t any_align;
 };
 
 // Tag / extra addresses of record i.
@@ -591,6 +596,75 @@ struct DtlsSetWindow {
   uint64_t *block_s;
 };
 int launch_dtls_set_window(const DtlsSetWindow &p, void *stream);
+// QUIC packet protection (quic.hip, quic_prepare.h; BSSL_AMD_QUIC_AEAD): what
+// one direction of one key generation of a connection keeps on the device.
+struct alignas(16) QuicState {
+  // Open: the largest authenticated packet number + 1, 0 before any packet.
+  uint64_t expected;
+  uint64_t pad;
+  // The header-protection key, as DtlsState::sn.
+  uint32_t hp[60];
+  uint32_t pad2[4];
+};
+static_assert(sizeof(QuicState) == 16 + 256, "layout");
+constexpr uint64_t kQuicMaxPacketNumber = (uint64_t(1) << 62) - 1;
+// Step 1 of a batch (quic_prepare_kernel), one lane per packet.  Seal: the
+// header into `out` with the packet-number length bits and field of pn =
+// next_pn + i.  Open: the mask from the sample, the unmasked header into `out`,
+// the decoded packet number, the tag into tags + 16 i.  Both: the nonce, the
+// body's offset and length and the header length for the bulk kernels (a packet
+// that fails here: length 0, valid 0).
+struct QuicPrepare {
+  uint64_t n;
+  const uint8_t *in;
+  uint8_t *out;
+  const uint64_t *offsets;     // or i * packet_stride
+  const uint64_t *lengths;     // or packet_len for all
+  uint64_t packet_stride;
+  uint64_t packet_len;
+  const uint32_t *pn_offsets;  // or pn_offset for all
+  uint32_t pn_offset;
+  const uint8_t *pn_lengths;   // seal: or pn_length for all
+  uint8_t pn_length;
+  uint8_t iv[12];
+  uint64_t next_pn;            // seal
+  int open;
+  uint8_t *nonces, *valid;
+  uint8_t *tags;               // open: 16 bytes per packet
+  uint64_t *body_offsets, *body_lengths, *ad_lengths;
+  uint64_t *pns;               // open: the decoded numbers, for the state step
+  uint32_t *header_lengths;    // open, or null
+  uint64_t *packet_numbers;    // or null
+  const QuicState *state;
+};
+int launch_quic_prepare(const QuicPrepare &p, int mask, void *stream);
+// After a seal: the tag from tags + 16 i to the packet's end, the 5-byte mask
+// of the sample onto the first byte and the packet-number field of every
+// packet with status[i] != 0; the whole slot of a failed one zeroed.
+struct QuicProtect {
+  uint64_t n;
+  uint8_t *out;
+  const uint64_t *offsets;
+  const uint64_t *lengths;
+  uint64_t packet_stride;
+  uint64_t packet_len;
+  const uint64_t *body_offsets, *body_lengths;
+  const uint8_t *tags;
+  const uint8_t *status;
+  uint64_t *out_lengths;  // or null
+  const QuicState *state;
+};
+int launch_quic_protect(const QuicProtect &p, int mask, void *stream);
+// Step 3 of an open: out_lengths[i], and expected = max(expected, 1 + pns[i])
+// over the packets with status[i] != 0.
+struct QuicExpected {
+  uint64_t n;
+  const uint8_t *status;
+  const uint64_t *pns, *body_lengths;
+  uint64_t *out_lengths;  // or null
+  QuicState *state;
+};
+int launch_quic_expected(const QuicExpected &p, void *stream);
 // Record-layer limits (include/openssl/ssl3.h of the reference).
 constexpr uint64_t kTlsMaxPlainLen = 16384;
 constexpr uint64_t kTlsMaxEncryptedLen = 16384 + 320;

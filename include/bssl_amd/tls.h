@@ -610,6 +610,145 @@ BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_open_records_device(BSSL_AMD_DTLS_SET *s,
                                                           const BSSL_AMD_DTLS_SET_RECORDS *r,
                                                           void *hip_stream);
 
+/* ---- QUIC packet protection (RFC 9001 5) -----------------------------------
+ *
+ * BSSL_AMD_QUIC_AEAD is one direction of one key generation of one QUIC
+ * connection: the AEAD of RFC 9001 5.3 and the header protection of 5.4 for a
+ * batch of packets -- what a QUIC stack otherwise does with one
+ * EVP_AEAD_CTX_seal / _open and one AES or ChaCha20 block per packet.  An
+ * opening context keeps `expected` -- the largest authenticated packet number
+ * + 1, or 0 before any packet -- on the device, so that both calls only enqueue
+ * work on hip_stream, for AES-GCM too.  The state of a context lives in stream
+ * order: issue all calls of one context on one stream, or order them as if
+ * they were.  The AEAD is the plain one, as for DTLS: the context generates its
+ * own packet numbers, so its nonces rise strictly by construction.
+ *
+ * Packets are contiguous, header ++ ciphertext ++ tag in one piece: packet i
+ * occupies offsets[i] .. + lengths[i] of `in`, and the same offsets apply to
+ * `out`.  O = pn_offsets[i] is the number of header bytes before the
+ * packet-number field, N (1..4) the length of that field, pn the packet
+ * number:
+ *   form    the first byte's top bit: set, a long header, whose first-byte
+ *           mask is 0x0f; clear, a short header, mask 0x1f
+ *   nonce   iv XOR (0^4 ++ be64(pn))
+ *   AD      the unprotected header through the packet-number field, O + N bytes
+ *   tag     16 bytes
+ *   mask    (RFC 9001 5.4) sample = the 16 bytes at packet offset O + 4 of the
+ *           protected packet.  AES suites: the first 5 bytes of AES-ECB(hp_key,
+ *           sample); ChaCha20: the first 5 keystream bytes of ChaCha20 with key
+ *           hp_key, block counter le32(sample[0..4)), nonce sample[4..16).
+ *           byte0 ^= mask[0] & (0x0f or 0x1f); pn byte k ^= mask[1 + k], k < N
+ *
+ * Seal.  lengths[i] = header + payload; the caller leaves lengths[i] + 16
+ * bytes of room in `out`.  The input is the header (O + N bytes, N =
+ * pn_lengths[i]) ++ the payload.  Packet i gets pn = next_packet_number() + i
+ * and the context advances by n; a packet that fails alone still consumes its
+ * number.  The device replaces bits 0..1 of the first byte with N - 1 and the N
+ * field bytes with the low N bytes of pn, big-endian, and changes nothing else
+ * in the header: the fixed bit, the reserved bits and the key phase are the
+ * caller's.  It then seals the payload, writes the tag after it and applies
+ * the mask.  A packet fails alone -- status 0, out_lengths[i] 0, all
+ * lengths[i] + 16 bytes of its slot in `out` zero -- when N is not in 1..4, O
+ * == 0, O + N > lengths[i], or N + the payload length < 4 (the sample would
+ * run past the tag; RFC 9001 5.4.2 has the sender pad).  Otherwise
+ * out_lengths[i] = lengths[i] + 16.  packet_numbers[i] = pn for every packet.
+ * Returns 0 with ERR_R_OVERFLOW and nothing launched when
+ * next_packet_number() + n - 1 > 2^62 - 1.
+ *
+ * Open.  lengths[i] = the whole protected packet.  Let E be `expected` at the
+ * point of the stream where the call's work runs.
+ *  1. Parse.  The packet fails when O == 0 or lengths[i] < O + 20 (no room for
+ *     the sample).  Otherwise the mask is computed from the sample, the first
+ *     byte unmasked, N = (byte0 & 3) + 1, N field bytes unmasked and pn =
+ *     decode(E, truncated, 8 N) exactly as RFC 9000 A.3: win = 2^(8N), hwin =
+ *     win / 2, cand = (E & ~(win - 1)) | truncated; if cand + hwin <= E and
+ *     cand < 2^62 - win then cand += win, else if cand > E + hwin and cand >=
+ *     win then cand -= win.  A packet that fails here has status 0, its
+ *     outputs 0, and nothing of its slot in `out` is written.
+ *  2. The AEAD.  The unprotected header, H = O + N bytes, is written to `out`
+ *     for every parsed packet whether or not it authenticates: that is how the
+ *     caller reads the key-phase and reserved bits.  The AEAD opens the
+ *     lengths[i] - H - 16 ciphertext bytes with that header as AD; the
+ *     plaintext goes to out + offsets[i] + H.  A packet that does not
+ *     authenticate gets that many zero bytes, status 0 and out_lengths[i] 0;
+ *     otherwise out_lengths[i] = the payload length.  header_lengths[i] = H
+ *     and packet_numbers[i] = pn for every parsed packet.  The last 16 bytes
+ *     of the slot in `out` are never written by open.
+ *  3. The state.  expected = max(E, 1 + max pn over the packets that
+ *     authenticated), on the device.  Packets that failed never move it.
+ *
+ * One deliberate departure, the DTLS one: every packet of a call is decoded
+ * against E, not against the running maximum, so that a forged packet cannot
+ * disturb its neighbours and step 1 stays parallel.  A conforming sender's
+ * encoding (RFC 9000 17.1) is decodable against any value between its largest
+ * acknowledged number and the packet itself, so this holds for conforming
+ * peers.  For packets in order the bound per call is 128, 32768, 2^23 or 2^31
+ * packets past E for N = 1, 2, 3, 4; a longer run is issued as several calls
+ * back to back on the stream, each of which sees the `expected` the one before
+ * it left.
+ *
+ * Argument errors of both calls: a NULL context, packets, or `in` / `out` with
+ * packets present, or on seal a uniform pn_length outside 1..4 (pn_lengths
+ * NULL), ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; the wrong direction
+ * CIPHER_R_INVALID_OPERATION.  num_packets == 0 returns 1.
+ *
+ * Out of scope: duplicate detection (RFC 9000 12.3) is the caller's, and
+ * packet_numbers serves it; key update -- a context is one key generation, the
+ * header-protection key does not change with a key update, so either
+ * generation's context unmasks the header and the caller routes by the
+ * key-phase bit; Retry and Version Negotiation packets; parsing long headers
+ * or coalesced datagrams to find O and the length; AES-128-CCM; sets of
+ * connections. */
+typedef struct bssl_amd_quic_aead_st BSSL_AMD_QUIC_AEAD;
+
+/* `aead`: EVP_aead_aes_128_gcm(), EVP_aead_aes_256_gcm() or
+ * EVP_aead_chacha20_poly1305().  iv: 12 bytes; hp_key: the header-protection
+ * key of EVP_AEAD_key_length(aead) bytes.  next_pn: the first packet number of
+ * a sealing context (ignored on open, whose `expected` starts at 0).  Checked
+ * before any GPU call: a NULL aead, key, iv or hp_key, or next_pn > 2^62 - 1 is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; the AES-CTR-HMAC and CBC AEADs
+ * CIPHER_R_CTRL_NOT_IMPLEMENTED; any other AEAD, or a wrong key_len, iv_len or
+ * hp_key_len, CIPHER_R_UNSUPPORTED_KEY_SIZE. */
+BSSL_AMD_EXPORT BSSL_AMD_QUIC_AEAD *BSSL_AMD_QUIC_AEAD_new(
+    enum evp_aead_direction_t direction, const EVP_AEAD *aead, const uint8_t *key, size_t key_len,
+    const uint8_t *iv, size_t iv_len, const uint8_t *hp_key, size_t hp_key_len, uint64_t next_pn);
+/* Waits for the device, zeroes the key material and the state on it. */
+BSSL_AMD_EXPORT void BSSL_AMD_QUIC_AEAD_free(BSSL_AMD_QUIC_AEAD *q);
+/* Seal: the packet number the next packet will use. */
+BSSL_AMD_EXPORT uint64_t BSSL_AMD_QUIC_AEAD_next_packet_number(const BSSL_AMD_QUIC_AEAD *q);
+/* `expected` of an opening context (a sealing one: CIPHER_R_INVALID_OPERATION);
+ * both synchronise hip_stream.  A value above 2^62 is
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED. */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_get_expected(BSSL_AMD_QUIC_AEAD *q, uint64_t *expected,
+                                                    void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_set_expected(BSSL_AMD_QUIC_AEAD *q, uint64_t expected,
+                                                    void *hip_stream);
+
+typedef struct {
+  size_t num_packets;
+  const uint8_t *in;       /* device */
+  uint8_t *out;            /* device, may equal in */
+  const uint64_t *offsets; /* device, or NULL: i * packet_stride */
+  const uint64_t *lengths; /* device, or NULL: packet_len */
+  uint64_t packet_stride;
+  uint64_t packet_len;
+  const uint32_t *pn_offsets; /* device, or NULL: pn_offset for every packet */
+  uint32_t pn_offset;
+  const uint8_t *pn_lengths; /* seal only; device, or NULL: pn_length for every packet */
+  uint8_t pn_length;
+  uint8_t *status;          /* device, 1 / 0 per packet, or NULL */
+  uint64_t *out_lengths;    /* device, optional */
+  uint32_t *header_lengths; /* device, optional; open only */
+  uint64_t *packet_numbers; /* device, optional */
+} BSSL_AMD_QUIC_PACKETS;
+
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_seal_packets_device(BSSL_AMD_QUIC_AEAD *q,
+                                                           const BSSL_AMD_QUIC_PACKETS *p,
+                                                           void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_open_packets_device(BSSL_AMD_QUIC_AEAD *q,
+                                                           const BSSL_AMD_QUIC_PACKETS *p,
+                                                           void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

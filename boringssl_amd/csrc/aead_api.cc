@@ -759,13 +759,13 @@ uint8_t *tls_nonce_flags(const EVP_AEAD_CTX *ctx, const uint8_t *nonces, size_t 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   CtxState *st = state_of(ctx);
   uint8_t *valid = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&valid), n, s) != hipSuccess) {
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&valid), n, s) != hipSuccess) {
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
     return nullptr;
   }
   if (tls_nonce_scan(nonces, n, ctx->aead->tls, &st->min_next_nonce, &st->mask, valid, 0,
                      stream) != 0) {
-    hipFreeAsync(valid, s);
+    bssl_amd::scratch_free(valid, s);
     PUT_ERROR(ERR_R_INTERNAL_ERROR);
     return nullptr;
   }
@@ -1392,7 +1392,7 @@ int EVP_AEAD_CTX_seal_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_BATCH
                                    hip_stream);
   if (!valid) return 0;
   const int ok = run_batch(st->km, ctx->tag_len, batch, false, false, hip_stream, valid);
-  hipFreeAsync(valid, reinterpret_cast<hipStream_t>(hip_stream));
+  bssl_amd::scratch_free(valid, reinterpret_cast<hipStream_t>(hip_stream));
   return ok;
 }
 
@@ -1484,7 +1484,7 @@ int EVP_AEAD_CTX_sealv_batch_device(const EVP_AEAD_CTX *ctx, const BSSL_AMD_IOV_
   const int rc = iov_batch_run(iov_desc(batch),
                                KeyRunner(st->km, ctx->tag_len, false, hip_stream, valid),
                                hip_stream);
-  if (valid) hipFreeAsync(valid, s);
+  if (valid) bssl_amd::scratch_free(valid, s);
   if (rc != 0) {
     PUT_ERROR(ERR_R_INTERNAL_ERROR);
     return 0;

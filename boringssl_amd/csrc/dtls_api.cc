@@ -52,7 +52,7 @@ struct DtlsScratch {
     if (open)
       for (table_slots = 512; table_slots < 2 * n;) table_slots *= 2;
     const uint64_t words = 3 * n + 2 * table_slots + nb + 5;
-    if (hipMallocAsync(reinterpret_cast<void **>(&buf), 8 * words + n * (12 + ad_stride + 3), s) !=
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf), 8 * words + n * (12 + ad_stride + 3), s) !=
         hipSuccess) {
       buf = nullptr;
       PUT_ERROR(ERR_R_MALLOC_FAILURE);
@@ -71,7 +71,7 @@ struct DtlsScratch {
     types = status + n;
   }
   ~DtlsScratch() {
-    if (buf) hipFreeAsync(buf, s);
+    if (buf) bssl_amd::scratch_free(buf, s);
   }
   DtlsScratch(const DtlsScratch &) = delete;
   DtlsScratch &operator=(const DtlsScratch &) = delete;

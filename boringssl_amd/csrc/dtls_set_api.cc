@@ -58,7 +58,7 @@ struct SetScratch {
       for (table_slots = 512; table_slots < 2 * n;) table_slots *= 2;
     const uint64_t words8 = 3 * n + 1 + 7 * wruns + nb;
     const uint64_t words4 = 2 * n + runs + nb + table_slots;
-    if (hipMallocAsync(reinterpret_cast<void **>(&buf),
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf),
                        8 * words8 + 4 * words4 + n * (12 + ad_stride + 3), s) != hipSuccess) {
       buf = nullptr;
       PUT_ERROR(ERR_R_MALLOC_FAILURE);
@@ -85,7 +85,7 @@ struct SetScratch {
     types = status + n;
   }
   ~SetScratch() {
-    if (buf) hipFreeAsync(buf, s);
+    if (buf) bssl_amd::scratch_free(buf, s);
   }
   SetScratch(const SetScratch &) = delete;
   SetScratch &operator=(const SetScratch &) = delete;

@@ -1264,23 +1264,23 @@ int launch_nr(const GcmKeyDev *keys, const BatchDesc &b, hipStream_t s, const Ke
   if (!num_cus) return 1;
   // The unit counters of the one-key kernels (64 bytes each, zeroed).
   uint32_t *units = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&units), 64, s) != hipSuccess) return 2;
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&units), 64, s) != hipSuccess) return 2;
   if (hipMemsetAsync(units, 0, 64, s) != hipSuccess) {
-    hipFreeAsync(units, s);
+    bssl_amd::scratch_free(units, s);
     return 2;
   }
   BatchDesc bo = b;  // with the processing order of a ragged batch
   uint32_t *order = nullptr;
   if (wants_length_order(b)) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
                        s) != hipSuccess) {
-      hipFreeAsync(units, s);
+      bssl_amd::scratch_free(units, s);
       return 2;
     }
     const int orc = build_length_order(b.lengths, b.num_records, order, order + b.num_records, s);
     if (orc) {
-      hipFreeAsync(order, s);
-      hipFreeAsync(units, s);
+      bssl_amd::scratch_free(order, s);
+      bssl_amd::scratch_free(units, s);
       return orc;
     }
     bo.order = order;
@@ -1339,8 +1339,8 @@ int launch_nr(const GcmKeyDev *keys, const BatchDesc &b, hipStream_t s, const Ke
   }
   int rc = (int)hipGetLastError();
   if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  if (order) hipFreeAsync(order, s);
-  hipFreeAsync(units, s);
+  if (order) bssl_amd::scratch_free(order, s);
+  bssl_amd::scratch_free(units, s);
   return rc;
 }
 

@@ -1191,27 +1191,27 @@ int launch_gcm_bs(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr, 
   const size_t ctl_bytes = 256;
   const size_t scratch_bytes = 2 * ctl_bytes + n * 32;
   uint8_t *scratch = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&scratch), scratch_bytes, s) != hipSuccess)
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&scratch), scratch_bytes, s) != hipSuccess)
     return 2;
   uint32_t *ctl = reinterpret_cast<uint32_t *>(scratch);
   uint32_t *ctl2 = reinterpret_cast<uint32_t *>(scratch + ctl_bytes);
   uint4 *ek0 = reinterpret_cast<uint4 *>(scratch + 2 * ctl_bytes);
   if (hipMemsetAsync(scratch, 0, scratch_bytes, s) != hipSuccess) {
-    hipFreeAsync(scratch, s);
+    bssl_amd::scratch_free(scratch, s);
     return 2;
   }
   BatchDesc bo = b;  // with the processing order of a ragged batch
   uint32_t *order = nullptr;
   if (wants_length_order(b)) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&order), (n + 128) * sizeof(uint32_t), s) !=
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&order), (n + 128) * sizeof(uint32_t), s) !=
         hipSuccess) {
-      hipFreeAsync(scratch, s);
+      bssl_amd::scratch_free(scratch, s);
       return 2;
     }
     const int orc = build_length_order(b.lengths, n, order, order + n, s);
     if (orc) {
-      hipFreeAsync(order, s);
-      hipFreeAsync(scratch, s);
+      bssl_amd::scratch_free(order, s);
+      bssl_amd::scratch_free(scratch, s);
       return orc;
     }
     bo.order = order;
@@ -1310,8 +1310,8 @@ int launch_gcm_bs(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr, 
             h[10], h[11], h[12], h[13], h[14], h[15]);
   }
 #endif
-  if (order) hipFreeAsync(order, s);
-  hipFreeAsync(scratch, s);
+  if (order) bssl_amd::scratch_free(order, s);
+  bssl_amd::scratch_free(scratch, s);
   return rc;
 }
 #endif  // BSSL_AMD_MIX_TU

@@ -111,9 +111,9 @@ int launch_gcm_mix(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nb,
   const int num_cus = device_cu_count();
   if (!num_cus) return 1;
   uint32_t *ctl = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&ctl), 64, s) != hipSuccess) return 2;
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&ctl), 64, s) != hipSuccess) return 2;
   if (hipMemsetAsync(ctl, 0, 64, s) != hipSuccess) {
-    hipFreeAsync(ctl, s);
+    bssl_amd::scratch_free(ctl, s);
     return 2;
   }
   if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->start), s);
@@ -136,7 +136,7 @@ int launch_gcm_mix(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nb,
 #undef BSSL_MIX
   const int rc = (int)hipGetLastError();
   if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  hipFreeAsync(ctl, s);
+  bssl_amd::scratch_free(ctl, s);
   return rc;
 }
 

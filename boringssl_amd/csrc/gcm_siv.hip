@@ -505,9 +505,9 @@ int launch_gcm_siv(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr,
   const int num_cus = device_cu_count();
   if (!num_cus) return 1;
   uint32_t *units = nullptr;  // the grid-wide unit counter
-  if (hipMallocAsync(reinterpret_cast<void **>(&units), 64, s) != hipSuccess) return 2;
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&units), 64, s) != hipSuccess) return 2;
   if (hipMemsetAsync(units, 0, 64, s) != hipSuccess) {
-    hipFreeAsync(units, s);
+    bssl_amd::scratch_free(units, s);
     return 2;
   }
   const uint64_t wanted = (b.num_records + kRecs - 1) / kRecs;
@@ -528,7 +528,7 @@ int launch_gcm_siv(const GcmKeyDev *keys, const BatchDesc &b, bool open, int nr,
   }
   const int rc = (int)hipGetLastError();
   if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  hipFreeAsync(units, s);
+  bssl_amd::scratch_free(units, s);
   return rc;
 }
 

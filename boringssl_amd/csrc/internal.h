@@ -29,6 +29,13 @@
 
 namespace bssl_amd {
 
+// The scratch block of a batch call, alive in stream order from the call's
+// first kernel to its last (scratch.cc): what hipMallocAsync / hipFreeAsync
+// promise, without the host wait that HIP's pool adds when it recycles a block
+// on a busy stream.  Neither call waits for the stream.
+hipError_t scratch_alloc(void **out, size_t bytes, hipStream_t stream);
+hipError_t scratch_free(void *ptr, hipStream_t stream);
+
 struct alignas(16) GcmKeyDev {
   // Round keys as little-endian words of the FIPS-197 schedule bytes; the
   // middle rounds (1..nr-1) are stored rotated left by 16 bits, which is how

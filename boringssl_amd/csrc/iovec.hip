@@ -42,7 +42,7 @@ int iov_batch_run(const IovBatchDesc &b, const IovRunner &run, void *stream) {
   const uint64_t n = b.num_records;
   if (n == 0) return 0;
   uint64_t *meta = nullptr;  // len, ad_len (n each)
-  if (hipMallocAsync(reinterpret_cast<void **>(&meta), 2 * n * 8 + 64, s) != hipSuccess) return 2;
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&meta), 2 * n * 8 + 64, s) != hipSuccess) return 2;
   uint64_t *len = meta, *ad_len = meta + n;
   hipLaunchKernelGGL(iov_lengths, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b, len,
                      ad_len);
@@ -59,7 +59,7 @@ int iov_batch_run(const IovBatchDesc &b, const IovRunner &run, void *stream) {
   d.aadvecs = b.aadvecs;
   d.aadvec_start = b.aadvec_start;
   int rc = run(d);
-  hipFreeAsync(meta, s);
+  bssl_amd::scratch_free(meta, s);
   if (!rc && hipGetLastError() != hipSuccess) rc = 1;
   return rc;
 }

@@ -152,12 +152,12 @@ int launch_lane_kernel(const BatchDesc &b, bool supported, unsigned threads, boo
   BatchDesc bo = b;  // with the processing order of a ragged batch
   uint32_t *order = nullptr;
   if (wants_length_order(b)) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&order), (b.num_records + 128) * sizeof(uint32_t),
                        s) != hipSuccess)
       return 2;
     const int orc = build_length_order(b.lengths, b.num_records, order, order + b.num_records, s);
     if (orc) {
-      hipFreeAsync(order, s);
+      bssl_amd::scratch_free(order, s);
       return orc;
     }
     bo.order = order;
@@ -166,7 +166,7 @@ int launch_lane_kernel(const BatchDesc &b, bool supported, unsigned threads, boo
   launch(bo, (unsigned)grid, threads, s);
   const int rc = (int)hipGetLastError();
   if (ev) hipEventRecord(reinterpret_cast<hipEvent_t>(ev->stop), s);
-  if (order) hipFreeAsync(order, s);
+  if (order) bssl_amd::scratch_free(order, s);
   return rc;
 }
 

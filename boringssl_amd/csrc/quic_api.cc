@@ -41,7 +41,7 @@ struct QuicScratch {
   uint64_t *body_off, *body_len, *ad_len, *pns;
   uint8_t *tags, *nonce, *valid, *status;
   QuicScratch(hipStream_t stream, uint64_t n) : s(stream) {
-    if (hipMallocAsync(reinterpret_cast<void **>(&buf), n * (4 * 8 + 16 + 12 + 2), s) != hipSuccess) {
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf), n * (4 * 8 + 16 + 12 + 2), s) != hipSuccess) {
       buf = nullptr;
       PUT_ERROR(ERR_R_MALLOC_FAILURE);
       return;
@@ -56,7 +56,7 @@ struct QuicScratch {
     status = valid + n;
   }
   ~QuicScratch() {
-    if (buf) hipFreeAsync(buf, s);
+    if (buf) bssl_amd::scratch_free(buf, s);
   }
   QuicScratch(const QuicScratch &) = delete;
   QuicScratch &operator=(const QuicScratch &) = delete;

@@ -119,7 +119,7 @@ struct TlsScratch {
              uint32_t type_len, bool keys, bool padded = false)
       : s(stream) {
     const uint32_t key_len = keys ? 4 : 0, frag = padded ? 8 : 0, status_len = padded ? 1 : 0;
-    if (hipMallocAsync(reinterpret_cast<void **>(&buf),
+    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf),
                        n * (frag + key_len + nonce_len + ad_stride + type_len + 1 + status_len),
                        s) != hipSuccess) {
       buf = nullptr;
@@ -135,7 +135,7 @@ struct TlsScratch {
     if (padded) status = valid + n;
   }
   ~TlsScratch() {
-    if (buf) hipFreeAsync(buf, s);
+    if (buf) bssl_amd::scratch_free(buf, s);
   }
   TlsScratch(const TlsScratch &) = delete;
   TlsScratch &operator=(const TlsScratch &) = delete;

@@ -86,7 +86,7 @@ int tls_nonce_scan(const uint8_t *nonces, uint64_t n, int tls, uint64_t *min_nex
     return 1;
   const size_t bytes = 64 + 2 * n * sizeof(uint64_t) + temp;
   uint8_t *buf = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void **>(&buf), bytes, s) != hipSuccess) return 2;
+  if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf), bytes, s) != hipSuccess) return 2;
   uint64_t *d_state = reinterpret_cast<uint64_t *>(buf);
   uint64_t *x = d_state + 8;
   uint64_t *prefix = x + n;
@@ -117,7 +117,7 @@ int tls_nonce_scan(const uint8_t *nonces, uint64_t n, int tls, uint64_t *min_nex
       *mask = out[1];
     }
   }
-  hipFreeAsync(buf, s);
+  bssl_amd::scratch_free(buf, s);
   if (!rc && hipGetLastError() != hipSuccess) rc = 1;
   return rc;
 }

@@ -106,6 +106,11 @@ EXPORTED_SYMBOLS = [
     "BSSL_AMD_QUIC_AEAD_new", "BSSL_AMD_QUIC_AEAD_free", "BSSL_AMD_QUIC_AEAD_next_packet_number",
     "BSSL_AMD_QUIC_AEAD_get_expected", "BSSL_AMD_QUIC_AEAD_set_expected",
     "BSSL_AMD_QUIC_AEAD_seal_packets_device", "BSSL_AMD_QUIC_AEAD_open_packets_device",
+    "BSSL_AMD_QUIC_SET_new", "BSSL_AMD_QUIC_SET_free", "BSSL_AMD_QUIC_SET_num_slots",
+    "BSSL_AMD_QUIC_SET_set_slots", "BSSL_AMD_QUIC_SET_clear_slots",
+    "BSSL_AMD_QUIC_SET_next_packet_numbers", "BSSL_AMD_QUIC_SET_get_expected",
+    "BSSL_AMD_QUIC_SET_set_expected", "BSSL_AMD_QUIC_SET_seal_packets_device",
+    "BSSL_AMD_QUIC_SET_open_packets_device",
 ]
 TLS13_TAG_LEN = 16  # BSSL_AMD_TLS13_TAG_LEN: the suffix stride of the padded calls
 TLS1_1_VERSION = 0x0302
@@ -305,6 +310,17 @@ _SIGS = {
                                                     _P]),
     "BSSL_AMD_QUIC_AEAD_open_packets_device": (_I, [_P, ctypes.POINTER(BSSL_AMD_QUIC_PACKETS),
                                                     _P]),
+    # (the packet calls take a BSSL_AMD_QUIC_SET_PACKETS, quic_set.py)
+    "BSSL_AMD_QUIC_SET_new": (_P, [_I, _P, _S]),
+    "BSSL_AMD_QUIC_SET_free": (None, [_P]),
+    "BSSL_AMD_QUIC_SET_num_slots": (_S, [_P]),
+    "BSSL_AMD_QUIC_SET_set_slots": (_I, [_P, _S, _S, _P, _P, _P, _P, _P]),
+    "BSSL_AMD_QUIC_SET_clear_slots": (_I, [_P, _S, _S, _P]),
+    "BSSL_AMD_QUIC_SET_next_packet_numbers": (_I, [_P, _S, _S, _P, _P]),
+    "BSSL_AMD_QUIC_SET_get_expected": (_I, [_P, _S, _S, _P, _P]),
+    "BSSL_AMD_QUIC_SET_set_expected": (_I, [_P, _S, _S, _P, _P]),
+    "BSSL_AMD_QUIC_SET_seal_packets_device": (_I, [_P, _P, _P]),
+    "BSSL_AMD_QUIC_SET_open_packets_device": (_I, [_P, _P, _P]),
 }
 for _name in EXPORTED_SYMBOLS:
     _f = getattr(_lib, _name)
@@ -1098,3 +1114,7 @@ def set_device(dev):
 
 def device_count():
     return _lib.BSSL_AMD_device_count()
+
+
+# BSSL_AMD_QUIC_SET lives in its own submodule; re-exported here.
+from .quic_set import BSSL_AMD_QUIC_SET_PACKETS, QuicSet, make_quic_set_packets  # noqa: E402,F401

@@ -17,7 +17,7 @@
 //                            slot's epoch, IV, S[c] + k or window maximum and
 //                            record-number key.  That key differs lane by lane:
 //                            the AES masks read their round keys from the lane's
-//                            odd-stride LDS slot (lane_frame.h) beside the
+//                            odd-stride LDS slot (set_lanes.h) beside the
 //                            bank-replicated T-table, ChaCha20's key words come
 //                            from the slot into registers
 //   dtls_set_advance_kernel  one thread per run: the winner of a live slot in a
@@ -66,39 +66,13 @@
 #include "internal.h"
 #include "dtls_prepare.h"
 #include "lane_frame.h"
+#include "set_lanes.h"
 #include "wave_bytes.h"
 
 namespace bssl_amd {
 namespace {
 
-constexpr int kThreads = 256;
-
-// The workgroup's LDS of a kernel that computes masks with a key per lane: for
-// the AES suites the T-table and 256 slots of 4 (NR + 1) + 1 words.
-struct SetNoLds {
-  uint32_t t[1][2][32];
-};
-template <int MASK>
-constexpr int set_nr() {
-  return MASK == kDtlsMaskAes256 ? 14 : 10;
-}
-template <int MASK>
-using SetLds = std::conditional_t<dtls_mask_is_aes(MASK), LaneLds<set_nr<MASK>(), true, kThreads>, SetNoLds>;
-static_assert(sizeof(SetLds<kDtlsMaskAes256>) == 64 * 1024 + kThreads * 61 * 4 &&
-                  sizeof(SetLds<kDtlsMaskAes256>) <= 160 * 1024 &&
-                  sizeof(SetLds<kDtlsMaskAes128>) <= 160 * 1024,
-              "LDS per workgroup");
-
-// The record-number key of a lane: the slot's words (ChaCha20: read into
-// registers by dtls_mask16), or for AES the lane's LDS slot filled from them.
-// Every thread of the workgroup calls this (the barrier).
-template <int MASK>
-__device__ __forceinline__ const uint32_t *set_sn_key(const DtlsSetSlot &sl, SetLds<MASK> &L) {
-  if constexpr (dtls_mask_is_aes(MASK))
-    return lane_round_keys<set_nr<MASK>(), true>(sl.sn, L);
-  else
-    return sl.sn;
-}
+constexpr int kThreads = kSetThreads;
 
 // The records of run j: run_start[j+1] - run_start[j], 0 for a decreasing pair.
 __device__ __forceinline__ uint64_t run_count(const DtlsSetPrepare &p, uint64_t j) {
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void dtls_set_prepare_kernel(DtlsSetPrepa
     ok = s0 <= kDtlsMaxSequence && k <= kDtlsMaxSequence - s0;
     seq = s0 + k;
   }
-  const uint32_t *sn = set_sn_key<MASK>(sl, L);
+  const uint32_t *sn = set_mask_key<MASK>(sl.sn, L);
   if (i >= r.n) return;
   p.run_of[i] = ok ? (uint32_t)j + 1 : 0;
   p.key_index[i] = ok ? c : 0;
@@ -215,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void dtls_set_mask_kernel(DtlsMaskSeal p,
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool act = i < p.n && p.status[i] != 0;
   const uint32_t c = act ? key_index[i] : 0;
-  const uint32_t *sn = set_sn_key<MASK>(slots[c < num_slots ? c : 0], L);
+  const uint32_t *sn = set_mask_key<MASK>(slots[c < num_slots ? c : 0].sn, L);
   if (!act) return;
   const uint64_t len = p.lengths ? p.lengths[i] : p.record_len;
   const uint64_t off = p.offsets ? p.offsets[i] : i * p.record_stride;
@@ -229,40 +203,11 @@ __global__ __launch_bounds__(kThreads) void dtls_set_mask_kernel(DtlsMaskSeal p,
 
 constexpr uint32_t kEmpty = ~0u;
 
-// (run + 1, sequence number), ordered lexicographically; (0, 0): no record.
-struct RunSeq {
-  uint32_t r;
-  uint64_t s;
-};
-
-__device__ __forceinline__ RunSeq rs_max(RunSeq a, RunSeq b) {
-  return (b.r > a.r || (b.r == a.r && b.s > a.s)) ? b : a;
-}
-
-__device__ __forceinline__ RunSeq rs_shfl_up(RunSeq v, int d) {
-  RunSeq u;
-  u.r = (uint32_t)__shfl_up((int)v.r, d);
-  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v.s, d);
-  const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v.s >> 32), d);
-  u.s = ((uint64_t)hi << 32) | lo;
-  return u;
-}
-
 __device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
 __device__ __forceinline__ uint64_t key_slot(RunSeq v, uint64_t slots) {
   const uint64_t x = v.s * 0x9e3779b97f4a7c15ull + (uint64_t)v.r * 0xc2b2ae3d27d4eb4full;
   return (x >> 20) & (slots - 1);
-}
-
-// The inclusive prefix maximum of v over the wave's lanes.
-__device__ __forceinline__ RunSeq wave_scan_max(RunSeq v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const RunSeq u = rs_shfl_up(v, d);
-    if (lane >= d) v = rs_max(v, u);
-  }
-  return v;
 }
 
 // The exclusive prefix maximum of v over a workgroup of THREADS threads ((0, 0)

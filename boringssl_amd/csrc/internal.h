@@ -672,6 +672,60 @@ struct QuicExpected {
   QuicState *state;
 };
 int launch_quic_expected(const QuicExpected &p, void *stream);
+// QUIC connection sets (quic_set.hip; BSSL_AMD_QUIC_SET): what a slot -- one
+// direction of one key generation of one packet-number space of one connection
+// -- keeps on the device.  All zero: unset.
+struct alignas(16) QuicSetSlot {
+  // Seal: the next packet number S, 2^62: exhausted.  Open: `expected`.
+  uint64_t pn;
+  // The IV as TlsSetConn has it.
+  uint64_t iv_lo;
+  uint32_t iv_hi;
+  uint32_t live;   // 1: keys and IV installed
+  // Within one call: ~j of the lowest non-empty run j that names this slot
+  // (atomicMax; 0: none).  0 between calls.
+  uint32_t claim;
+  uint32_t pad;
+  // The header-protection key, as QuicState::hp.
+  uint32_t hp[60];
+};
+static_assert(sizeof(QuicSetSlot) == 32 + 240, "layout");
+// One batch over many slots: packets [run_start[j], run_start[j+1]) belong to
+// slot run_slot[j].  pk.iv, pk.next_pn and pk.state are unused (they come from
+// the slot); pk.valid, pk.pns (open) and key_index are written for every
+// packet.  flag, run_of, run_won: as DtlsSetPrepare's.
+struct QuicSetPrepare {
+  QuicPrepare pk;
+  QuicSetSlot *slots;
+  uint32_t num_slots;
+  uint64_t num_runs;
+  const uint32_t *run_slot;
+  const uint64_t *run_start;  // num_runs + 1 entries
+  uint32_t *key_index;
+  uint32_t *flag;
+  uint32_t *run_of;
+  uint32_t *run_won;
+};
+// Three launches in stream order: the runs claim their slots and check
+// run_start, every packet is prepared from its slot (or failed), the runs that
+// won advance their slots' packet numbers (seal) and clear the claims.
+int launch_quic_set_prepare(const QuicSetPrepare &p, int mask, void *stream);
+// After a seal: QuicProtect with packet i's header-protection key in
+// slots[key_index[i]] (m.state is unused).
+int launch_quic_set_protect(const QuicProtect &m, const QuicSetSlot *slots, uint32_t num_slots,
+                            const uint32_t *key_index, int mask, void *stream);
+// Step 3 of an open over a set: out_lengths[i], and for every run that won its
+// slot, the slot's expected = max(expected, 1 + pns[i]) over the run's packets
+// with status[i] != 0 (e.state is unused).
+struct QuicSetExpected {
+  QuicExpected e;
+  QuicSetSlot *slots;
+  uint32_t num_slots;
+  uint64_t num_runs;
+  const uint32_t *run_of;
+  const uint32_t *run_won;
+};
+int launch_quic_set_expected(const QuicSetExpected &p, void *stream);
 // Record-layer limits (include/openssl/ssl3.h of the reference).
 constexpr uint64_t kTlsMaxPlainLen = 16384;
 constexpr uint64_t kTlsMaxEncryptedLen = 16384 + 320;

@@ -697,8 +697,8 @@ BSSL_AMD_EXPORT int BSSL_AMD_DTLS_SET_open_records_device(BSSL_AMD_DTLS_SET *s,
  * header-protection key does not change with a key update, so either
  * generation's context unmasks the header and the caller routes by the
  * key-phase bit; Retry and Version Negotiation packets; parsing long headers
- * or coalesced datagrams to find O and the length; AES-128-CCM; sets of
- * connections. */
+ * or coalesced datagrams to find O and the length; AES-128-CCM.  Many
+ * connections in one call: BSSL_AMD_QUIC_SET below. */
 typedef struct bssl_amd_quic_aead_st BSSL_AMD_QUIC_AEAD;
 
 /* `aead`: EVP_aead_aes_128_gcm(), EVP_aead_aes_256_gcm() or
@@ -748,6 +748,132 @@ BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_seal_packets_device(BSSL_AMD_QUIC_AEAD *q
 BSSL_AMD_EXPORT int BSSL_AMD_QUIC_AEAD_open_packets_device(BSSL_AMD_QUIC_AEAD *q,
                                                            const BSSL_AMD_QUIC_PACKETS *p,
                                                            void *hip_stream);
+
+/* ---- QUIC connection sets: one packet batch across many connections --------
+ *
+ * BSSL_AMD_QUIC_SET is one direction of up to num_slots slots of ONE AEAD
+ * suite.  A slot is what a BSSL_AMD_QUIC_AEAD is -- one direction of one key
+ * generation of one packet-number space of one connection -- with all of its
+ * state on the device: the AEAD key, the IV, the expanded header-protection
+ * key and one 64-bit number, the next packet number S[c] (seal) or expected[c]
+ * (open).  The caller maps (connection, space, key generation) to slots.  One
+ * call protects a batch that mixes the packets of many slots and only enqueues
+ * work on hip_stream: seal and open never synchronise it, not for AES-GCM
+ * either.  The state of a set lives in stream order: issue all calls of one
+ * set on one stream, or order them as if they were.
+ *
+ * Packets [run_start[j], run_start[j+1]) of a batch belong to slot
+ * c = run_slot[j]; the packet layout is BSSL_AMD_QUIC_PACKETS's.
+ *
+ * Equivalence.  For a well-formed batch, everything written for the packets of
+ * run j -- the packet's slot in `out`, status, out_lengths, header_lengths,
+ * packet_numbers -- and the slot's number afterwards are byte for byte what
+ * BSSL_AMD_QUIC_AEAD_new(direction, aead, key_c, iv_c, hp_c, S[c]), on open
+ * with `expected` set to the slot's, produces for those packets in order in
+ * one call.  That includes the batch-start rule: every packet of a run is
+ * decoded against ITS SLOT's `expected` at the point of the stream where the
+ * call's work runs, so the 128 / 32768 / 2^23 / 2^31 in-order bound holds per
+ * slot per call, not per call.
+ *
+ * Seal.  Packet k of run j gets pn = S[c] + k, and S[c] advances by the run's
+ * packet count, on the device.  A packet that fails in the one-connection
+ * layer (N outside 1..4, O == 0, O + N > lengths[i], N + payload < 4) still
+ * consumes its number, as it does there.  A packet whose number would pass
+ * 2^62 - 1 fails alone as below, and S[c] saturates at 2^62 (exhausted): the
+ * one-connection call returns ERR_R_OVERFLOW as a whole there, a set does not
+ * let one exhausted connection fail the others.
+ *
+ * Open.  expected[c] = max(E_c, 1 + max pn over the run's packets that
+ * authenticated), on the device.  Packets that fail never move it, and a
+ * packet in another run never moves it either, whatever number it decodes to.
+ *
+ * Packets that fail alone, besides those that fail in the one-connection
+ * layer; they consume no number and leave the slot's `expected` untouched:
+ *   - run_slot[j] is out of range, or the slot is unset or cleared;
+ *   - the slot already has an earlier non-empty run in this call: the lowest j
+ *     wins, and the slot moves by the winning run only.
+ * On seal such a packet looks like a one-connection failed packet: status 0,
+ * out_lengths[i] 0, all lengths[i] + 16 bytes of its slot in `out` zero, and
+ * packet_numbers[i] 0.  On open it looks like a one-connection parse failure:
+ * status, out_lengths, header_lengths and packet_numbers 0, and nothing of its
+ * slot in `out` is written.
+ *
+ * Malformed run_start.  As for BSSL_AMD_DTLS_SET: when run_start is not
+ * non-decreasing, or run_start[0] != 0, or run_start[num_runs] != num_packets,
+ * every packet of the call fails as above and no slot changes.  Nothing
+ * outside the batch's arrays is read or written, whatever run_start and
+ * run_slot hold.  (The check runs on the device: the call itself still
+ * returns 1.)
+ *
+ * Out of scope: key update as an operation -- a new key generation is a fresh
+ * slot, installed with the `numbers` the caller's ACK state already knows;
+ * duplicate detection; Retry and Version Negotiation packets; mixed suites in
+ * one set; more than one run per slot per call; finding O. */
+typedef struct bssl_amd_quic_set_st BSSL_AMD_QUIC_SET;
+
+/* The aead rules and codes of BSSL_AMD_QUIC_AEAD_new: a NULL aead, or
+ * num_slots 0 or above 2^32 - 2, is ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; the
+ * AES-CTR-HMAC and CBC AEADs CIPHER_R_CTRL_NOT_IMPLEMENTED; any other AEAD than
+ * AES-128-GCM, AES-256-GCM or ChaCha20-Poly1305 CIPHER_R_UNSUPPORTED_KEY_SIZE.
+ * All checks come before any GPU call.  All slots start unset. */
+BSSL_AMD_EXPORT BSSL_AMD_QUIC_SET *BSSL_AMD_QUIC_SET_new(enum evp_aead_direction_t direction,
+                                                         const EVP_AEAD *aead, size_t num_slots);
+/* Waits for the device, zeroes the key material and the slots on it and frees
+ * it. */
+BSSL_AMD_EXPORT void BSSL_AMD_QUIC_SET_free(BSSL_AMD_QUIC_SET *s);
+BSSL_AMD_EXPORT size_t BSSL_AMD_QUIC_SET_num_slots(const BSSL_AMD_QUIC_SET *s);
+
+/* (Re)key slots first .. first+n-1 from HOST arrays: n keys, n 12-byte IVs, n
+ * header-protection keys of the key's length, n numbers (seal: the first
+ * packet numbers; open: `expected`; NULL: all 0).  Ordered on hip_stream like
+ * BSSL_AMD_DTLS_SET_set_slots, and waits for it: the host copies of the key
+ * material are zeroed before the call returns.  Checked before any GPU call,
+ * all ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED: a slot range outside the set, NULL
+ * keys, ivs or hp_keys, a number above 2^62 - 1 (seal) or above 2^62 (open). */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_set_slots(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
+                                                const uint8_t *keys, const uint8_t *ivs,
+                                                const uint8_t *hp_keys, const uint64_t *numbers,
+                                                void *hip_stream);
+/* Unset slots: key material and number zeroed on the device, in stream order;
+ * their packets then fail.  Only enqueues work. */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_clear_slots(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
+                                                  void *hip_stream);
+/* A sealing set: the next packet numbers of slots first..first+n-1 to HOST
+ * memory (0 for an unset slot, 2^62 for an exhausted one); synchronises
+ * hip_stream.  An opening set: CIPHER_R_INVALID_OPERATION. */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_next_packet_numbers(BSSL_AMD_QUIC_SET *s, size_t first,
+                                                          size_t n, uint64_t *out,
+                                                          void *hip_stream);
+/* An opening set: `expected` of slots first..first+n-1, HOST arrays; both
+ * synchronise hip_stream.  With them a live connection moves onto the set.  A
+ * value above 2^62 is ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED; a sealing set
+ * CIPHER_R_INVALID_OPERATION. */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_get_expected(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
+                                                   uint64_t *out, void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_set_expected(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
+                                                   const uint64_t *expected, void *hip_stream);
+
+typedef struct {
+  BSSL_AMD_QUIC_PACKETS packets; /* layout exactly as for one connection;
+                                    at most 2^32 - 2 packets */
+  size_t num_runs;               /* at most 2^32 - 2 */
+  const uint32_t *run_slot;      /* device, num_runs entries */
+  const uint64_t *run_start; /* device, num_runs + 1 entries, non-decreasing,
+                                run_start[0] = 0, run_start[num_runs] = num_packets */
+} BSSL_AMD_QUIC_SET_PACKETS;
+
+/* Seal (open) the batch; see above.  Returns 0 with nothing launched and an
+ * error queued for argument errors: a NULL set, packets, or `in` / `out` with
+ * packets present, num_runs == 0 with num_packets != 0, missing run arrays, a
+ * count above 2^32 - 2, on seal a uniform pn_length outside 1..4 (all
+ * ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED), the wrong direction
+ * (CIPHER_R_INVALID_OPERATION).  num_packets == 0 returns 1. */
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_seal_packets_device(BSSL_AMD_QUIC_SET *s,
+                                                          const BSSL_AMD_QUIC_SET_PACKETS *p,
+                                                          void *hip_stream);
+BSSL_AMD_EXPORT int BSSL_AMD_QUIC_SET_open_packets_device(BSSL_AMD_QUIC_SET *s,
+                                                          const BSSL_AMD_QUIC_SET_PACKETS *p,
+                                                          void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
-// api_internal.h -- what the host C-ABI sources share: aead_api.cc defines it,
-// tls_api.cc (the record layer of bssl_amd/tls.h) uses it.  Host only; the
-// kernels see internal.h alone.
+// api_internal.h -- what the host C-ABI sources share: aead_api.cc defines it;
+// the record and packet layers of bssl_amd/tls.h (tls_api.cc, dtls_api.cc,
+// quic_api.cc and the sets, set_api.h) use it, with the argument and result
+// helpers below.  Host only; the kernels see internal.h alone.
 #ifndef BSSL_AMD_API_INTERNAL_H
 #define BSSL_AMD_API_INTERNAL_H
 
@@ -25,6 +26,22 @@ namespace bssl_amd {
 void put_error(int reason);
 #define PUT_ERROR(reason) ::bssl_amd::put_error(reason)
 
+// The argument and result helpers of the calls of bssl_amd/tls.h: each queues
+// its error and returns false (finish: 0).
+inline bool fail(int reason) {
+  PUT_ERROR(reason);
+  return false;
+}
+// A call without its context, set or a required array.
+inline bool present(const void *p) { return p ? true : fail(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED); }
+// A context or set of the other direction was called, or a call reads or
+// writes what only the other direction keeps.
+inline bool direction_ok(bool seal, bool want_seal) {
+  return seal == want_seal ? true : fail(CIPHER_R_INVALID_OPERATION);
+}
+// The end of a call whose GPU work was enqueued (or not).
+inline int finish(bool ok) { return ok ? 1 : (int)fail(ERR_R_INTERNAL_ERROR); }
+
 // Device-resident key material for one or more keys.
 struct KeyMaterial {
   const EVP_AEAD *aead;
@@ -38,6 +55,13 @@ struct KeyMaterial {
   // kAeadTlsCbc: the one direction the keys work in (e_tls.cc:125-129, 274-278).
   bool open_only = false;
 };
+
+// Whether slots first .. first + n - 1 are inside the set t (its keyset t->km).
+template <class Set>
+bool range_ok(const Set *t, size_t first, size_t n) {
+  if (t && first <= t->km->num_keys && n <= t->km->num_keys - first) return true;
+  return fail(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
+}
 
 // Makes `dev` the calling thread's current HIP device for the guard's scope
 // and restores the previous one (host-buffer calls may come from any thread,
@@ -83,7 +107,7 @@ int launch_desc(const KeyMaterial *km, const BatchDesc &d, bool open, void *stre
 // until the next pair is taken.
 const KernelEvents *kernel_timing_pair();
 // Brackets the launches of one step of a call with such a pair (dtls_api.cc,
-// dtls_set_api.cc).
+// the sets).
 struct Timed {
   const KernelEvents *ev;
   hipStream_t s;

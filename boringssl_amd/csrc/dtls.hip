@@ -237,16 +237,6 @@ __global__ __launch_bounds__(256) void dtls_window_apply_kernel(DtlsWindow p) {
   }
 }
 
-template <class F>
-void with_mask(int mask, F &&f) {
-  switch (mask) {
-    case kDtlsMaskAes128: f(std::integral_constant<int, kDtlsMaskAes128>{}); break;
-    case kDtlsMaskAes256: f(std::integral_constant<int, kDtlsMaskAes256>{}); break;
-    case kDtlsMaskChaCha: f(std::integral_constant<int, kDtlsMaskChaCha>{}); break;
-    default: f(std::integral_constant<int, kDtlsMaskNone>{}); break;
-  }
-}
-
 }  // namespace
 
 int launch_dtls_prepare(const DtlsPrepare &p, int mask, void *stream) {

@@ -77,19 +77,9 @@ struct DtlsScratch {
   DtlsScratch &operator=(const DtlsScratch &) = delete;
 };
 
-bool present(const void *p) {
-  if (p) return true;
-  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-  return false;
-}
-
 // The checks both record calls share; false with the error queued.
 bool dtls_args_ok(const BSSL_AMD_DTLS_AEAD *t, const BSSL_AMD_DTLS_RECORDS *r, bool want_seal) {
-  if (!present(t)) return false;
-  if (t->seal != want_seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return false;
-  }
+  if (!present(t) || !direction_ok(t->seal, want_seal)) return false;
   if (r && (r->num_records == 0 ||
             (r->in && r->out && r->prefix && r->suffix &&
              !(!want_seal && t->dtls13 && !r->out_lengths))))
@@ -146,12 +136,6 @@ BatchDesc batch_desc(const BSSL_AMD_DTLS_AEAD *t, const BSSL_AMD_DTLS_RECORDS *r
   d.num_keys = 1;
   d.valid = sc.valid;
   return d;
-}
-
-int finish(bool ok) {
-  if (ok) return 1;
-  PUT_ERROR(ERR_R_INTERNAL_ERROR);
-  return 0;
 }
 
 int dtls_seal(BSSL_AMD_DTLS_AEAD *t, const BSSL_AMD_DTLS_RECORDS *r, void *stream) {
@@ -331,15 +315,7 @@ BSSL_AMD_DTLS_AEAD *BSSL_AMD_DTLS_AEAD_new(enum evp_aead_direction_t direction, 
   // once (the kernels read it with scalar loads).
   DtlsState host;
   memset(&host, 0, sizeof(host));
-  bool ok = true;
-  if (t->mask == kDtlsMaskChaCha) {
-    for (int k = 0; k < 32; k++) host.sn[k / 4] |= (uint32_t)sn_key[k] << (8 * (k & 3));
-  } else if (t->mask != kDtlsMaskNone) {
-    CbcKeyDev ks;
-    ok = cbc_key_setup(sn_key, sn_key_len, &ks);
-    memcpy(host.sn, ks.rk, sizeof(host.sn));
-    secure_zero(&ks, sizeof(ks));
-  }
+  bool ok = mask_key_words(t->mask, sn_key, sn_key_len, host.sn);
   ok = ok && hipMalloc(reinterpret_cast<void **>(&t->state), sizeof(DtlsState)) == hipSuccess;
   if (!ok) t->state = nullptr;
   ok = ok && hipMemcpy(t->state, &host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess;

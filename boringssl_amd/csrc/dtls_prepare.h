@@ -12,6 +12,8 @@
 #ifndef BSSL_AMD_DTLS_PREPARE_H
 #define BSSL_AMD_DTLS_PREPARE_H
 
+#include <type_traits>
+
 #include "internal.h"
 #include "chacha_block.h"
 #include "iov_dev.h"  // (before rec_blocks.h: mask_block)
@@ -22,6 +24,18 @@ namespace bssl_amd {
 namespace {
 
 constexpr bool dtls_mask_is_aes(int mask) { return mask == kDtlsMaskAes128 || mask == kDtlsMaskAes256; }
+
+// Host: calls f with the DtlsMask as a compile-time constant, for the launchers
+// of the kernels that are instantiated per mask.
+template <class F>
+void with_mask(int mask, F &&f) {
+  switch (mask) {
+    case kDtlsMaskAes128: f(std::integral_constant<int, kDtlsMaskAes128>{}); break;
+    case kDtlsMaskAes256: f(std::integral_constant<int, kDtlsMaskAes256>{}); break;
+    case kDtlsMaskChaCha: f(std::integral_constant<int, kDtlsMaskChaCha>{}); break;
+    default: f(std::integral_constant<int, kDtlsMaskNone>{}); break;
+  }
+}
 
 // The first 16 bytes of fragment || tag (RFC 9147 4.2.3's sample), as
 // little-endian words: a fragment shorter than 16 bytes continues in the tag

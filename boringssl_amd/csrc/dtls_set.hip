@@ -3,36 +3,23 @@
 // slots, each one direction of one epoch of one association.  A slot's fixed
 // IV, epoch, record-number key, write sequence number and replay window live
 // on the device (DtlsSetSlot); records [run_start[j], run_start[j+1]) belong
-// to slot c = run_slot[j].  The composition of tls_set.hip's claim / prepare /
-// advance scheme, dtls_prepare.h's per-record body and dtls.hip's parallel
-// window, the window now one per slot.
+// to slot c = run_slot[j].  The run-to-slot frame -- the claim, the search,
+// the failure rules, the advance of the write sequence number (seal only,
+// saturating at 2^48) -- is set_runs.h's, in its strict form; dtls_prepare.h
+// has the per-record body and the windows are dtls.hip's parallel form, one
+// per slot.
 //
-//   dtls_set_claim_kernel    one thread per run: the claim of tls_set.hip
-//                            (atomicMax of ~j, the lowest j wins) and the check
-//                            of run_start -- non-decreasing, from 0 to n -- into
-//                            one flag word
-//   dtls_set_prepare_kernel  one lane per record: its run (binary search), the
-//                            failure rules into valid[i], key_index[i],
-//                            run_of[i], then dtls_prepare_record with the
+//   dtls_set_prepare_kernel  one lane per record: set_lane(), then key_index[i],
+//                            run_of[i] and dtls_prepare_record with the
 //                            slot's epoch, IV, S[c] + k or window maximum and
 //                            record-number key.  That key differs lane by lane:
 //                            the AES masks read their round keys from the lane's
 //                            odd-stride LDS slot (set_lanes.h) beside the
 //                            bank-replicated T-table, ChaCha20's key words come
 //                            from the slot into registers
-//   dtls_set_advance_kernel  one thread per run: the winner of a live slot in a
-//                            well-formed batch is noted in run_won[j] and, on
-//                            seal, advances S[c], saturating at 2^48; the claim
-//                            word is cleared
 //   dtls_set_mask_kernel     after a DTLS 1.3 seal: dtls_mask_kernel with the
 //                            lane's own key
 //   dtls_set_window_*        the replay windows, below
-//
-// Nothing outside the batch's arrays is read or written, whatever run_start
-// and run_slot hold: run_start's values are only compared with record indices,
-// a record is worked on only when run_start[j] <= i < run_start[j+1] for the j
-// the search returns (always below num_runs), and a slot is touched only when
-// run_slot[j] < num_slots.  With the flag set no record is worked on at all.
 //
 // The windows.  The sequential definition, per slot: for the run's records
 // that authenticated, in index order, refuse record i if ShouldDiscard(s_i),
@@ -67,6 +54,7 @@
 #include "dtls_prepare.h"
 #include "lane_frame.h"
 #include "set_lanes.h"
+#include "set_runs.h"
 #include "wave_bytes.h"
 
 namespace bssl_amd {
@@ -74,70 +62,26 @@ namespace {
 
 constexpr int kThreads = kSetThreads;
 
-// The records of run j: run_start[j+1] - run_start[j], 0 for a decreasing pair.
-__device__ __forceinline__ uint64_t run_count(const DtlsSetPrepare &p, uint64_t j) {
-  const uint64_t lo = p.run_start[j], hi = p.run_start[j + 1];
-  return hi > lo ? hi - lo : 0;
-}
-
-__global__ void dtls_set_claim_kernel(DtlsSetPrepare p) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p.num_runs) return;
-  const uint64_t lo = p.run_start[j], hi = p.run_start[j + 1];
-  if (hi < lo || (j == 0 && lo != 0) || (j + 1 == p.num_runs && hi != p.rec.n)) atomicOr(p.flag, 1u);
-  const uint32_t c = p.run_slot[j];
-  if (c >= p.num_slots || hi <= lo) return;  // an empty run claims nothing
-  atomicMax(&p.slots[c].claim, ~(uint32_t)j);
-}
-
 template <int MASK>
 __global__ __launch_bounds__(kThreads) void dtls_set_prepare_kernel(DtlsSetPrepare p) {
   __shared__ SetLds<MASK> L;
   if constexpr (dtls_mask_is_aes(MASK)) lane_fill_tables(L, kAesTables.te0, kThreads);
   const DtlsPrepare &r = p.rec;
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  bool ok = i < r.n && *p.flag == 0;
-  uint64_t j = 0, start = 0;
-  uint32_t c = 0;
-  if (ok) {
-    // The last run that starts at or before record i (empty runs share their
-    // start with the next run and are passed over).
-    uint64_t lo = 0, hi = p.num_runs;  // the answer is in [lo, hi)
-    while (hi - lo > 1) {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (p.run_start[mid] <= i)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    j = lo;
-    start = p.run_start[j];
-    ok = start <= i && i < p.run_start[j + 1];
-  }
-  if (ok) {
-    c = p.run_slot[j];
-    ok = c < p.num_slots;
-  }
-  const DtlsSetSlot &sl = p.slots[ok ? c : 0];
-  uint64_t seq = 0;
-  // Live, and this run is the slot's first in the call.
-  if (ok) ok = sl.live == 1 && sl.claim == ~(uint32_t)j;
-  if (ok && !r.open) {
-    // HasNext (dtls_record.cc:500-505), record by record.
-    const uint64_t k = i - start, s0 = sl.seq;
-    ok = s0 <= kDtlsMaxSequence && k <= kDtlsMaxSequence - s0;
-    seq = s0 + k;
-  }
+  // (Only a seal consumes sequence numbers.)
+  const SetLane l = set_lane(p.runs, p.slots, r.n, i, !r.open);
+  const DtlsSetSlot &sl = p.slots[l.c];
+  // Every thread of the workgroup reaches the LDS fill.
   const uint32_t *sn = set_mask_key<MASK>(sl.sn, L);
   if (i >= r.n) return;
-  p.run_of[i] = ok ? (uint32_t)j + 1 : 0;
-  p.key_index[i] = ok ? c : 0;
-  if (ok) {
+  p.runs.run_of[i] = l.ok ? (uint32_t)l.j + 1 : 0;
+  p.runs.key_index[i] = l.ok ? l.c : 0;
+  if (l.ok) {
     // (A DTLS 1.3 seal's flag is the pre-pass's, tls_pad.hip; an open's is
     // written by the body.)
     if (!r.open && !r.dtls13) r.valid[i] = 1;
     const TlsIv iv = {sl.iv_lo, sl.iv_hi};
-    dtls_prepare_record<MASK>(r, i, sl.epoch, seq, iv, sl.max_seq, sn, L);
+    dtls_prepare_record<MASK>(r, i, sl.epoch, l.number, iv, sl.max_seq, sn, L);
     return;
   }
   // A record without a slot: the bulk kernel zeroes its outputs (valid 0); its
@@ -154,29 +98,6 @@ __global__ __launch_bounds__(kThreads) void dtls_set_prepare_kernel(DtlsSetPrepa
     if (r.out_lengths) r.out_lengths[i] = 0;
     for (uint32_t b = 0; b < r.prefix_len; b++) r.prefix[(uint64_t)r.prefix_len * i + b] = 0;
   }
-}
-
-__global__ void dtls_set_advance_kernel(DtlsSetPrepare p) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p.num_runs) return;
-  const uint32_t c = p.run_slot[j];
-  const uint64_t cnt = run_count(p, j);
-  uint32_t won = 0;
-  if (c < p.num_slots && cnt != 0) {
-    DtlsSetSlot &sl = p.slots[c];
-    // Only the winner touches the slot, so no other thread of this launch
-    // reads or writes what it writes.
-    if (sl.claim == ~(uint32_t)j) {
-      if (*p.flag == 0 && sl.live == 1) {
-        won = c + 1;
-        const uint64_t s0 = sl.seq;
-        if (!p.rec.open && s0 <= kDtlsMaxSequence)
-          sl.seq = cnt > kDtlsMaxSequence + 1 - s0 ? kDtlsMaxSequence + 1 : s0 + cnt;
-      }
-      sl.claim = 0;
-    }
-  }
-  p.run_won[j] = won;
 }
 
 template <int MASK>
@@ -392,30 +313,18 @@ __global__ __launch_bounds__(256) void dtls_set_window_apply_kernel(DtlsSetWindo
   }
 }
 
-template <class F>
-void with_mask(int mask, F &&f) {
-  switch (mask) {
-    case kDtlsMaskAes128: f(std::integral_constant<int, kDtlsMaskAes128>{}); break;
-    case kDtlsMaskAes256: f(std::integral_constant<int, kDtlsMaskAes256>{}); break;
-    case kDtlsMaskChaCha: f(std::integral_constant<int, kDtlsMaskChaCha>{}); break;
-    default: f(std::integral_constant<int, kDtlsMaskNone>{}); break;
-  }
-}
-
 }  // namespace
 
 int launch_dtls_set_prepare(const DtlsSetPrepare &p, int mask, void *stream) {
-  if (p.rec.n == 0 || p.num_runs == 0) return 0;
+  if (p.rec.n == 0 || p.runs.num_runs == 0) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 run_grid((unsigned)((p.num_runs + 255) / 256));
   const dim3 grid((unsigned)((p.rec.n + kThreads - 1) / kThreads));
-  hipLaunchKernelGGL(dtls_set_claim_kernel, run_grid, dim3(256), 0, s, p);
-  // Only a DTLS 1.3 open computes masks in this step.
-  with_mask(p.rec.open && p.rec.dtls13 ? mask : kDtlsMaskNone, [&](auto m) {
-    hipLaunchKernelGGL(dtls_set_prepare_kernel<decltype(m)::value>, grid, dim3(kThreads), 0, s, p);
+  return launch_set_prepare(p.runs, p.slots, p.rec.n, p.rec.open, s, [&] {
+    // Only a DTLS 1.3 open computes masks in this step.
+    with_mask(p.rec.open && p.rec.dtls13 ? mask : kDtlsMaskNone, [&](auto m) {
+      hipLaunchKernelGGL(dtls_set_prepare_kernel<decltype(m)::value>, grid, dim3(kThreads), 0, s, p);
+    });
   });
-  hipLaunchKernelGGL(dtls_set_advance_kernel, run_grid, dim3(256), 0, s, p);
-  return (int)hipGetLastError();
 }
 
 int launch_dtls_set_mask(const DtlsMaskSeal &m, const DtlsSetSlot *slots, uint32_t num_slots,

@@ -404,18 +404,32 @@ struct alignas(16) TlsSetConn {
   uint32_t pad;
 };
 static_assert(sizeof(TlsSetConn) == 32, "layout");
-// A batch of records of many connections: records [run_start[j],
-// run_start[j+1]) belong to connection run_connection[j].  rec.fixed_iv and
-// rec.seq are unused (they come from conns[c]); rec.valid is written for every
-// record, and key_index[i] with its connection (0 for a record that has none).
+// The runs of a batch over a set (set_runs.h): records [run_start[j],
+// run_start[j+1]) belong to slot run_slot[j] of num_slots; key_index[i] is
+// written with record i's slot (0 for a record that has none).  Scratch of the
+// DTLS and QUIC sets alone (the TLS set has none of it and leaves them null):
+//   flag      one word, zero: set when run_start is malformed
+//   run_of    per record: j + 1 of the run whose slot the record was prepared
+//             with, 0 for a record that has none
+//   run_won   per run: c + 1 when run j won the live slot c in a well-formed
+//             batch, else 0 (the advance kernel, for the steps that follow)
+struct SetRuns {
+  uint32_t num_slots;
+  uint64_t num_runs;
+  const uint32_t *run_slot;
+  const uint64_t *run_start;  // num_runs + 1 entries
+  uint32_t *key_index;
+  uint32_t *flag;
+  uint32_t *run_of;
+  uint32_t *run_won;
+};
+// A batch of records of many connections.  rec.fixed_iv and rec.seq are unused
+// (they come from conns[c]); rec.valid and runs.key_index are written for every
+// record.
 struct TlsSetPrepare {
   TlsPrepare rec;
   TlsSetConn *conns;
-  uint32_t num_connections;
-  uint64_t num_runs;
-  const uint32_t *run_connection;
-  const uint64_t *run_start;  // num_runs + 1 entries
-  uint32_t *key_index;
+  SetRuns runs;
 };
 // Three launches in stream order: the runs claim their connections, every
 // record is prepared with its connection's next sequence number (or failed),
@@ -557,26 +571,13 @@ struct alignas(16) DtlsSetSlot {
   uint32_t sn[60];
 };
 static_assert(sizeof(DtlsSetSlot) == 80 + 240, "layout");
-// One batch over many slots: records [run_start[j], run_start[j+1]) belong to
-// slot run_slot[j].  rec.fixed_iv, rec.epoch, rec.seq and rec.state are unused
-// (they come from the slot); rec.valid, rec.seqs (open) and key_index are
-// written for every record.  Scratch, by the launchers' order of use:
-//   flag      one word, zero: set when run_start is malformed
-//   run_of    per record: j + 1 of the run whose slot the record was prepared
-//             with, 0 for a record that has none
-//   run_won   per run: c + 1 when run j won the live slot c in a well-formed
-//             batch, else 0 (the advance kernel, for the window)
+// One batch over many slots.  rec.fixed_iv, rec.epoch, rec.seq and rec.state
+// are unused (they come from the slot); rec.valid, rec.seqs (open) and
+// runs.key_index are written for every record.
 struct DtlsSetPrepare {
   DtlsPrepare rec;
   DtlsSetSlot *slots;
-  uint32_t num_slots;
-  uint64_t num_runs;
-  const uint32_t *run_slot;
-  const uint64_t *run_start;  // num_runs + 1 entries
-  uint32_t *key_index;
-  uint32_t *flag;
-  uint32_t *run_of;
-  uint32_t *run_won;
+  SetRuns runs;
 };
 // Three launches in stream order: the runs claim their slots and check
 // run_start, every record is prepared from its slot (or failed), the runs that
@@ -690,21 +691,13 @@ struct alignas(16) QuicSetSlot {
   uint32_t hp[60];
 };
 static_assert(sizeof(QuicSetSlot) == 32 + 240, "layout");
-// One batch over many slots: packets [run_start[j], run_start[j+1]) belong to
-// slot run_slot[j].  pk.iv, pk.next_pn and pk.state are unused (they come from
-// the slot); pk.valid, pk.pns (open) and key_index are written for every
-// packet.  flag, run_of, run_won: as DtlsSetPrepare's.
+// One batch over many slots.  pk.iv, pk.next_pn and pk.state are unused (they
+// come from the slot); pk.valid, pk.pns (open) and runs.key_index are written
+// for every packet.
 struct QuicSetPrepare {
   QuicPrepare pk;
   QuicSetSlot *slots;
-  uint32_t num_slots;
-  uint64_t num_runs;
-  const uint32_t *run_slot;
-  const uint64_t *run_start;  // num_runs + 1 entries
-  uint32_t *key_index;
-  uint32_t *flag;
-  uint32_t *run_of;
-  uint32_t *run_won;
+  SetRuns runs;
 };
 // Three launches in stream order: the runs claim their slots and check
 // run_start, every packet is prepared from its slot (or failed), the runs that
@@ -779,6 +772,10 @@ int gcm_key_setup_device(const uint8_t *keys, size_t key_len, size_t n, GcmKeyDe
 void chacha_key_setup(const uint8_t *key, ChaChaKeyDev *out);
 // AES-CCM / AES-EAX key (host only); false for a bad key length.
 bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out);
+// A record-number or header-protection key (DtlsMask `mask`) ORed into the
+// zeroed words of DtlsState::sn and its like: the AES schedule, or ChaCha20's
+// eight key words; nothing for kDtlsMaskNone.  false for a bad key length.
+bool mask_key_words(int mask, const uint8_t *key, size_t key_len, uint32_t out[60]);
 // AES-CTR-HMAC-SHA256 key, AES key || 32-byte HMAC key (host only); false for
 // a bad key length.
 bool ctr_hmac_key_setup(const uint8_t *key, size_t key_len, AesHmacKeyDev *out);

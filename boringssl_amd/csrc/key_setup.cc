@@ -74,6 +74,20 @@ bool cbc_key_setup(const uint8_t *key, size_t key_len, CbcKeyDev *out) {
   return true;
 }
 
+bool mask_key_words(int mask, const uint8_t *key, size_t key_len, uint32_t out[60]) {
+  if (mask == kDtlsMaskNone) return true;
+  if (mask == kDtlsMaskChaCha) {
+    for (int k = 0; k < 32; k++) out[k / 4] |= (uint32_t)key[k] << (8 * (k & 3));
+    return true;
+  }
+  CbcKeyDev ks;
+  const bool ok = cbc_key_setup(key, key_len, &ks);
+  static_assert(sizeof(ks.rk) == 60 * sizeof(uint32_t), "schedule");
+  if (ok) memcpy(out, ks.rk, sizeof(ks.rk));
+  secure_zero(&ks, sizeof(ks));
+  return ok;
+}
+
 namespace {
 
 // FIPS 180-4 6.2.2: one SHA-256 compression of the 64-byte block `blk` into

@@ -62,19 +62,9 @@ struct QuicScratch {
   QuicScratch &operator=(const QuicScratch &) = delete;
 };
 
-bool present(const void *p) {
-  if (p) return true;
-  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-  return false;
-}
-
 // The checks both batch calls share; false with the error queued.
 bool quic_args_ok(const BSSL_AMD_QUIC_AEAD *q, const BSSL_AMD_QUIC_PACKETS *p, bool want_seal) {
-  if (!present(q)) return false;
-  if (q->seal != want_seal) {
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return false;
-  }
+  if (!present(q) || !direction_ok(q->seal, want_seal)) return false;
   if (p && (p->num_packets == 0 ||
             (p->in && p->out &&
              !(want_seal && !p->pn_lengths && (p->pn_length < 1 || p->pn_length > 4)))))
@@ -133,12 +123,6 @@ BatchDesc batch_desc(const BSSL_AMD_QUIC_PACKETS *p, const QuicScratch &sc) {
   d.valid = sc.valid;
   d.any_align = 1;  // a body starts where its header ends
   return d;
-}
-
-int finish(bool ok) {
-  if (ok) return 1;
-  PUT_ERROR(ERR_R_INTERNAL_ERROR);
-  return 0;
 }
 
 int quic_seal(BSSL_AMD_QUIC_AEAD *q, const BSSL_AMD_QUIC_PACKETS *p, void *stream) {
@@ -277,15 +261,7 @@ BSSL_AMD_QUIC_AEAD *BSSL_AMD_QUIC_AEAD_new(enum evp_aead_direction_t direction,
   // The device state: expected 0 and the header-protection key, expanded once.
   QuicState host;
   memset(&host, 0, sizeof(host));
-  bool ok = true;
-  if (chacha) {
-    for (int k = 0; k < 32; k++) host.hp[k / 4] |= (uint32_t)hp_key[k] << (8 * (k & 3));
-  } else {
-    CbcKeyDev ks;
-    ok = cbc_key_setup(hp_key, hp_key_len, &ks);
-    memcpy(host.hp, ks.rk, sizeof(host.hp));
-    secure_zero(&ks, sizeof(ks));
-  }
+  bool ok = mask_key_words(q->mask, hp_key, hp_key_len, host.hp);
   ok = ok && hipMalloc(reinterpret_cast<void **>(&q->state), sizeof(QuicState)) == hipSuccess;
   if (!ok) q->state = nullptr;
   ok = ok && hipMemcpy(q->state, &host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess;

@@ -4,38 +4,26 @@
 // of one connection.  A slot's IV, header-protection key and number (the next
 // packet number S[c] on seal, expected[c] on open) live on the device
 // (QuicSetSlot); packets [run_start[j], run_start[j+1]) belong to slot
-// c = run_slot[j].  The composition of dtls_set.hip's claim / prepare / advance
-// scheme and quic_prepare.h's per-packet body.
+// c = run_slot[j].  The run-to-slot frame -- the claim, the search, the
+// failure rules, the advance of the packet number (seal only, saturating at
+// 2^62) -- is set_runs.h's, in its strict form; quic_prepare.h has the
+// per-packet body.
 //
-//   quic_set_claim_kernel     one thread per run: atomicMax of ~j on the slot's
-//                             claim (the lowest j wins) and the check of
-//                             run_start -- non-decreasing, from 0 to n -- into
-//                             one flag word
-//   quic_set_prepare_kernel   one lane per packet: its run (binary search), the
-//                             failure rules into valid[i], key_index[i],
-//                             run_of[i], then quic_seal_packet with S[c] + k or
-//                             quic_open_packet with the slot's expected, IV and
-//                             header-protection key.  That key differs lane by
-//                             lane: the AES masks read their round keys from the
-//                             lane's odd-stride LDS slot (set_lanes.h) beside
-//                             the bank-replicated T-table, ChaCha20's key words
-//                             come from the slot into registers
-//   quic_set_advance_kernel   one thread per run: the winner of a live slot in a
-//                             well-formed batch is noted in run_won[j] and, on
-//                             seal, advances S[c], saturating at 2^62; the claim
-//                             word is cleared
+//   quic_set_prepare_kernel   one lane per packet: set_lane(), then
+//                             key_index[i], run_of[i] and quic_seal_packet with
+//                             S[c] + k or quic_open_packet with the slot's
+//                             expected, IV and header-protection key.  That key
+//                             differs lane by lane: the AES masks read their
+//                             round keys from the lane's odd-stride LDS slot
+//                             (set_lanes.h) beside the bank-replicated T-table,
+//                             ChaCha20's key words come from the slot into
+//                             registers
 //   quic_set_protect_kernel   after a seal: quic_protect_kernel with the lane's
 //                             own key; a failed packet's slot zeroed
 //   quic_set_expected_kernel  after an open: out_lengths, and the maximum of
 //                             the authenticated packet numbers + 1 of every run
 //                             onto its slot (a segmented maximum within the
 //                             wave, one atomicMax per wave and run)
-//
-// Nothing outside the batch's arrays is read or written, whatever run_start
-// and run_slot hold: run_start's values are only compared with packet indices,
-// a packet is worked on only when run_start[j] <= i < run_start[j+1] for the j
-// the search returns (always below num_runs), and a slot is touched only when
-// run_slot[j] < num_slots.  With the flag set no packet is worked on at all.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -44,22 +32,13 @@
 #include "quic_prepare.h"
 #include "lane_frame.h"
 #include "set_lanes.h"
+#include "set_runs.h"
 #include "wave_bytes.h"
 
 namespace bssl_amd {
 namespace {
 
 constexpr int kThreads = kSetThreads;
-
-__global__ void quic_set_claim_kernel(QuicSetPrepare p) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p.num_runs) return;
-  const uint64_t lo = p.run_start[j], hi = p.run_start[j + 1];
-  if (hi < lo || (j == 0 && lo != 0) || (j + 1 == p.num_runs && hi != p.pk.n)) atomicOr(p.flag, 1u);
-  const uint32_t c = p.run_slot[j];
-  if (c >= p.num_slots || hi <= lo) return;  // an empty run claims nothing
-  atomicMax(&p.slots[c].claim, ~(uint32_t)j);
-}
 
 // MASK: kDtlsMaskNone for a seal (no mask in this step), the suite's for an open.
 template <int MASK>
@@ -68,47 +47,18 @@ __global__ __launch_bounds__(kThreads) void quic_set_prepare_kernel(QuicSetPrepa
   if constexpr (dtls_mask_is_aes(MASK)) lane_fill_tables(L, kAesTables.te0, kThreads);
   const QuicPrepare &r = p.pk;
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  bool ok = i < r.n && *p.flag == 0;
-  uint64_t j = 0, start = 0;
-  uint32_t c = 0;
-  if (ok) {
-    // The last run that starts at or before packet i (empty runs share their
-    // start with the next run and are passed over).
-    uint64_t lo = 0, hi = p.num_runs;  // the answer is in [lo, hi)
-    while (hi - lo > 1) {
-      const uint64_t mid = lo + (hi - lo) / 2;
-      if (p.run_start[mid] <= i)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    j = lo;
-    start = p.run_start[j];
-    ok = start <= i && i < p.run_start[j + 1];
-  }
-  if (ok) {
-    c = p.run_slot[j];
-    ok = c < p.num_slots;
-  }
-  const QuicSetSlot &sl = p.slots[ok ? c : 0];
-  uint64_t pn = 0;
-  // Live, and this run is the slot's first in the call.
-  if (ok) ok = sl.live == 1 && sl.claim == ~(uint32_t)j;
-  if (ok && MASK == kDtlsMaskNone) {
-    // The one-connection call's overflow rule, packet by packet.
-    const uint64_t k = i - start, s0 = sl.pn;
-    ok = s0 <= kQuicMaxPacketNumber && k <= kQuicMaxPacketNumber - s0;
-    pn = s0 + k;
-  }
+  // (Only a seal consumes packet numbers.)
+  const SetLane l = set_lane(p.runs, p.slots, r.n, i, MASK == kDtlsMaskNone);
+  const QuicSetSlot &sl = p.slots[l.c];
   // Every thread of the workgroup reaches the LDS fill.
   const uint32_t *hp = set_mask_key<MASK>(sl.hp, L);
   if (i >= r.n) return;
-  p.run_of[i] = ok ? (uint32_t)j + 1 : 0;
-  p.key_index[i] = ok ? c : 0;
-  if (ok) {
+  p.runs.run_of[i] = l.ok ? (uint32_t)l.j + 1 : 0;
+  p.runs.key_index[i] = l.ok ? l.c : 0;
+  if (l.ok) {
     const TlsIv iv = {sl.iv_lo, sl.iv_hi};
     if constexpr (MASK == kDtlsMaskNone)
-      quic_seal_packet(r, i, pn, iv);
+      quic_seal_packet(r, i, l.number, iv);
     else
       quic_open_packet<MASK>(r, i, iv, sl.pn, hp, L);
     return;
@@ -125,30 +75,6 @@ __global__ __launch_bounds__(kThreads) void quic_set_prepare_kernel(QuicSetPrepa
     r.pns[i] = 0;
   }
   quic_describe(r, i, k, false, 0, 0, zero, 0);
-}
-
-__global__ void quic_set_advance_kernel(QuicSetPrepare p) {
-  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p.num_runs) return;
-  const uint32_t c = p.run_slot[j];
-  const uint64_t lo = p.run_start[j], hi = p.run_start[j + 1];
-  const uint64_t cnt = hi > lo ? hi - lo : 0;
-  uint32_t won = 0;
-  if (c < p.num_slots && cnt != 0) {
-    QuicSetSlot &sl = p.slots[c];
-    // Only the winner touches the slot, so no other thread of this launch
-    // reads or writes what it writes.
-    if (sl.claim == ~(uint32_t)j) {
-      if (*p.flag == 0 && sl.live == 1) {
-        won = c + 1;
-        const uint64_t s0 = sl.pn;
-        if (!p.pk.open && s0 <= kQuicMaxPacketNumber)
-          sl.pn = cnt > kQuicMaxPacketNumber + 1 - s0 ? kQuicMaxPacketNumber + 1 : s0 + cnt;
-      }
-      sl.claim = 0;
-    }
-  }
-  p.run_won[j] = won;
 }
 
 template <int MASK>
@@ -207,31 +133,19 @@ __global__ __launch_bounds__(kThreads) void quic_set_expected_kernel(QuicSetExpe
   }
 }
 
-template <class F>
-void with_mask(int mask, F &&f) {
-  switch (mask) {
-    case kDtlsMaskAes128: f(std::integral_constant<int, kDtlsMaskAes128>{}); break;
-    case kDtlsMaskAes256: f(std::integral_constant<int, kDtlsMaskAes256>{}); break;
-    case kDtlsMaskChaCha: f(std::integral_constant<int, kDtlsMaskChaCha>{}); break;
-    default: f(std::integral_constant<int, kDtlsMaskNone>{}); break;
-  }
-}
-
 }  // namespace
 
 int launch_quic_set_prepare(const QuicSetPrepare &p, int mask, void *stream) {
-  if (p.pk.n == 0 || p.num_runs == 0) return 0;
+  if (p.pk.n == 0 || p.runs.num_runs == 0) return 0;
   if (p.pk.open && mask == kDtlsMaskNone) return 1;  // an open always has a mask
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 run_grid((unsigned)((p.num_runs + 255) / 256));
   const dim3 grid((unsigned)((p.pk.n + kThreads - 1) / kThreads));
-  hipLaunchKernelGGL(quic_set_claim_kernel, run_grid, dim3(256), 0, s, p);
-  // Only an open computes masks in this step.
-  with_mask(p.pk.open ? mask : kDtlsMaskNone, [&](auto m) {
-    hipLaunchKernelGGL(quic_set_prepare_kernel<decltype(m)::value>, grid, dim3(kThreads), 0, s, p);
+  return launch_set_prepare(p.runs, p.slots, p.pk.n, p.pk.open, s, [&] {
+    // Only an open computes masks in this step.
+    with_mask(p.pk.open ? mask : kDtlsMaskNone, [&](auto m) {
+      hipLaunchKernelGGL(quic_set_prepare_kernel<decltype(m)::value>, grid, dim3(kThreads), 0, s, p);
+    });
   });
-  hipLaunchKernelGGL(quic_set_advance_kernel, run_grid, dim3(256), 0, s, p);
-  return (int)hipGetLastError();
 }
 
 int launch_quic_set_protect(const QuicProtect &m, const QuicSetSlot *slots, uint32_t num_slots,

@@ -6,9 +6,10 @@
 // keyset plus one QuicSetSlot per slot on the device -- IV, header-protection
 // key, the next packet number or `expected` -- so that a batch that mixes the
 // packets of many connections is one call that only enqueues work: the claim /
-// prepare / advance kernels of quic_set.hip, the bulk kernels of the AEAD with
+// prepare / advance launches of quic_set.hip, the bulk kernels of the AEAD with
 // a key index per packet (launch_desc), then on seal the tag and the
-// header-protection mask, on open the per-slot `expected` update.
+// header-protection mask, on open the per-slot `expected` update.  The keyset,
+// the slot array and the scratch block are set_api.h's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -16,7 +17,7 @@
 #include <vector>
 
 #include "bssl_amd/tls.h"
-#include "api_internal.h"
+#include "set_api.h"
 
 using namespace bssl_amd;
 
@@ -32,72 +33,11 @@ namespace {
 constexpr uint32_t kTagLen = 16;
 constexpr size_t kMaxCount = 0xfffffffeu;  // slots, runs and packets of a call
 
-// The scratch of one call, one stream-ordered block freed in stream order on
-// every path.  Per packet: the body's offset and length, the header length,
-// the packet number (open), the tag, the key index, the run, the nonce, the
-// flag and a status byte for a caller who passes none; per run: who won; the
-// flag word (QuicSetPrepare).
-struct SetScratch {
-  hipStream_t s;
-  uint8_t *buf = nullptr;
-  uint64_t *body_off, *body_len, *ad_len, *pns, *zeroed;
-  uint32_t *flag, *key_index, *run_of, *run_won;
-  uint8_t *tags, *nonce, *valid, *status;
-  SetScratch(hipStream_t stream, uint64_t n, uint64_t runs) : s(stream) {
-    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf),
-                                n * (4 * 8 + 16 + 2 * 4 + 12 + 2) + 8 + 4 * runs, s) != hipSuccess) {
-      buf = nullptr;
-      PUT_ERROR(ERR_R_MALLOC_FAILURE);
-      return;
-    }
-    body_off = reinterpret_cast<uint64_t *>(buf);
-    body_len = body_off + n;
-    ad_len = body_len + n;
-    pns = ad_len + n;
-    tags = reinterpret_cast<uint8_t *>(pns + n);  // (16-byte aligned: 32 n bytes in)
-    zeroed = reinterpret_cast<uint64_t *>(tags + 16 * n);  // the flag word
-    flag = reinterpret_cast<uint32_t *>(zeroed);
-    key_index = reinterpret_cast<uint32_t *>(zeroed + 1);
-    run_of = key_index + n;
-    run_won = run_of + n;
-    nonce = reinterpret_cast<uint8_t *>(run_won + runs);
-    valid = nonce + 12 * n;
-    status = valid + n;
-  }
-  ~SetScratch() {
-    if (buf) bssl_amd::scratch_free(buf, s);
-  }
-  SetScratch(const SetScratch &) = delete;
-  SetScratch &operator=(const SetScratch &) = delete;
-};
-
-bool fail(int reason) {
-  PUT_ERROR(reason);
-  return false;
-}
-
-bool present(const void *p) { return p ? true : fail(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED); }
-
-int finish(bool ok) {
-  if (ok) return 1;
-  PUT_ERROR(ERR_R_INTERNAL_ERROR);
-  return 0;
-}
-
-// Whether slots first .. first + n - 1 are inside the set.
-bool range_ok(const BSSL_AMD_QUIC_SET *t, size_t first, size_t n) {
-  if (t && first <= t->km->num_keys && n <= t->km->num_keys - first) return true;
-  return fail(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-}
-
-// A call that reads or writes what only the other direction keeps.
-bool direction_ok(const BSSL_AMD_QUIC_SET *t, bool want_seal) {
-  return t->seal == want_seal ? true : fail(CIPHER_R_INVALID_OPERATION);
-}
+using Scratch = CallScratch<QuicSetLayout>;
 
 // The checks both packet calls share; false with the error queued.
 bool set_args_ok(const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp, bool want_seal) {
-  if (!present(t) || !direction_ok(t, want_seal)) return false;
+  if (!present(t) || !direction_ok(t->seal, want_seal)) return false;
   if (!sp) return fail(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
   const BSSL_AMD_QUIC_PACKETS *p = &sp->packets;
   if (p->num_packets == 0) return true;
@@ -110,7 +50,7 @@ bool set_args_ok(const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp
 }
 
 void fill_prepare(QuicSetPrepare *k, const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp,
-                  const SetScratch &sc) {
+                  const Scratch &sc) {
   const BSSL_AMD_QUIC_PACKETS *p = &sp->packets;
   memset(k, 0, sizeof(*k));
   k->pk.n = p->num_packets;
@@ -132,14 +72,8 @@ void fill_prepare(QuicSetPrepare *k, const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_
   k->pk.pns = sc.pns;
   k->pk.packet_numbers = p->packet_numbers;
   k->slots = t->slots;
-  k->num_slots = (uint32_t)t->km->num_keys;
-  k->num_runs = sp->num_runs;
-  k->run_slot = sp->run_slot;
-  k->run_start = sp->run_start;
-  k->key_index = sc.key_index;
-  k->flag = sc.flag;
-  k->run_of = sc.run_of;
-  k->run_won = sc.run_won;
+  k->runs = {(uint32_t)t->km->num_keys, sp->num_runs, sp->run_slot, sp->run_start,
+             sc.key_index,              sc.flag,      sc.run_of,    sc.run_won};
 }
 
 // The packets as the bulk kernels see them: record i is the body, its AD the
@@ -148,7 +82,7 @@ void fill_prepare(QuicSetPrepare *k, const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_
 // packets that have no slot, so the uniform-shape ChaCha20 seal shortcut of
 // quic_api.cc (which drops it) does not apply.
 BatchDesc batch_desc(const BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_PACKETS *p,
-                     const SetScratch &sc) {
+                     const Scratch &sc) {
   BatchDesc d;
   memset(&d, 0, sizeof(d));
   d.in = p->in;
@@ -181,14 +115,14 @@ int set_seal(BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp, void *st
   const KeyMaterial *km = t->km;
   if (!on_key_device(km)) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  SetScratch sc(s, n, sp->num_runs);
+  Scratch sc(s, n, sp->num_runs);
   if (!sc.buf) return 0;
   const BatchDesc d = batch_desc(t, p, sc);
   QuicSetPrepare k;
   fill_prepare(&k, t, sp, sc);
   k.pk.pn_lengths = p->pn_lengths;
   k.pk.pn_length = p->pn_length;
-  bool ok = hipMemsetAsync(sc.zeroed, 0, 8, s) == hipSuccess;
+  bool ok = hipMemsetAsync(sc.zeroed, 0, sc.zeroed_bytes, s) == hipSuccess;
   Timed prepare(s);
   ok = ok && launch_quic_set_prepare(k, t->mask, stream) == 0;
   prepare.stop();
@@ -198,7 +132,7 @@ int set_seal(BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp, void *st
     const QuicProtect m = {n,           p->out,      p->offsets, p->lengths, p->packet_stride,
                            p->packet_len, sc.body_off, sc.body_len, sc.tags,   d.status,
                            p->out_lengths, nullptr};
-    ok = launch_quic_set_protect(m, t->slots, k.num_slots, sc.key_index, t->mask, stream) == 0;
+    ok = launch_quic_set_protect(m, t->slots, k.runs.num_slots, sc.key_index, t->mask, stream) == 0;
     protect.stop();
   }
   return finish(ok);
@@ -211,13 +145,13 @@ int set_open(BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp, void *st
   const KeyMaterial *km = t->km;
   if (!on_key_device(km)) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  SetScratch sc(s, n, sp->num_runs);
+  Scratch sc(s, n, sp->num_runs);
   if (!sc.buf) return 0;
   const BatchDesc d = batch_desc(t, p, sc);
   QuicSetPrepare k;
   fill_prepare(&k, t, sp, sc);
   k.pk.header_lengths = p->header_lengths;
-  bool ok = hipMemsetAsync(sc.zeroed, 0, 8, s) == hipSuccess;
+  bool ok = hipMemsetAsync(sc.zeroed, 0, sc.zeroed_bytes, s) == hipSuccess;
   Timed prepare(s);
   ok = ok && launch_quic_set_prepare(k, t->mask, stream) == 0;
   prepare.stop();
@@ -225,27 +159,23 @@ int set_open(BSSL_AMD_QUIC_SET *t, const BSSL_AMD_QUIC_SET_PACKETS *sp, void *st
   if (ok) {
     Timed expected(s);
     const QuicSetExpected e = {{n, d.status, sc.pns, sc.body_len, p->out_lengths, nullptr},
-                               t->slots, k.num_slots, sp->num_runs, sc.run_of, sc.run_won};
+                               t->slots, k.runs.num_slots, sp->num_runs, sc.run_of, sc.run_won};
     ok = launch_quic_set_expected(e, stream) == 0;
     expected.stop();
   }
   return finish(ok);
 }
 
-// The slots' numbers to or from a packed host array; waits for the stream.
+// The slots' numbers to or from a packed host array (copy_columns, set_api.h).
 bool copy_numbers(BSSL_AMD_QUIC_SET *t, size_t first, size_t n, uint64_t *host, bool to_host,
                   hipStream_t s) {
-  uint8_t *dev = reinterpret_cast<uint8_t *>(t->slots + first) + offsetof(QuicSetSlot, pn);
-  const hipError_t e =
-      to_host ? hipMemcpy2DAsync(host, 8, dev, sizeof(QuicSetSlot), 8, n, hipMemcpyDeviceToHost, s)
-              : hipMemcpy2DAsync(dev, sizeof(QuicSetSlot), host, 8, 8, n, hipMemcpyHostToDevice, s);
-  // (The copy reads or writes the caller's frame: wait until it has.)
-  return hipStreamSynchronize(s) == hipSuccess && e == hipSuccess;
+  return copy_columns(t->slots, sizeof(QuicSetSlot), first, n, offsetof(QuicSetSlot, pn), 8, host,
+                      to_host, s);
 }
 
 int get_numbers(BSSL_AMD_QUIC_SET *s, size_t first, size_t n, uint64_t *out, bool want_seal,
                 void *hip_stream) {
-  if (!range_ok(s, first, n) || !direction_ok(s, want_seal)) return 0;
+  if (!range_ok(s, first, n) || !direction_ok(s->seal, want_seal)) return 0;
   if (n == 0) return 1;
   if (!present(out) || !on_key_device(s->km)) return 0;
   return finish(copy_numbers(s, first, n, out, true, reinterpret_cast<hipStream_t>(hip_stream)));
@@ -272,51 +202,22 @@ BSSL_AMD_QUIC_SET *BSSL_AMD_QUIC_SET_new(enum evp_aead_direction_t direction, co
     PUT_ERROR(CIPHER_R_UNSUPPORTED_KEY_SIZE);
     return nullptr;
   }
-  int dev = 0;
   BSSL_AMD_QUIC_SET *t = new (std::nothrow) bssl_amd_quic_set_st;
-  KeyMaterial *km = t ? new (std::nothrow) KeyMaterial{aead, 0, num_slots, 0, nullptr, 0} : nullptr;
-  if (!km || hipGetDevice(&dev) != hipSuccess) {
-    delete km;
+  if (t)
+    t->km = keyset_new(aead, num_slots, sizeof(QuicSetSlot), reinterpret_cast<void **>(&t->slots));
+  if (!t || !t->km) {
     delete t;
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
     return nullptr;
   }
-  km->device = dev;
-  km->nr = chacha ? 0 : (int)aead->key_len / 4 + 6;
-  km->bytes = num_slots * (chacha ? sizeof(ChaChaKeyDev) : sizeof(GcmKeyDev));
-  t->km = km;
-  t->slots = nullptr;
   t->seal = direction == evp_aead_seal;
   t->mask = chacha ? kDtlsMaskChaCha : aead->key_len == 16 ? kDtlsMaskAes128 : kDtlsMaskAes256;
-  // All slots unset: zero keys, zero state.
-  const size_t slot_bytes = num_slots * sizeof(QuicSetSlot);
-  bool ok = hipMalloc(&km->dev, km->bytes) == hipSuccess;
-  if (!ok) km->dev = nullptr;
-  ok = ok && hipMalloc(reinterpret_cast<void **>(&t->slots), slot_bytes) == hipSuccess;
-  ok = ok && hipMemset(km->dev, 0, km->bytes) == hipSuccess &&
-       hipMemset(t->slots, 0, slot_bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
-    if (t->slots) hipFree(t->slots);
-    if (km->dev) hipFree(km->dev);
-    delete km;
-    delete t;
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
   return t;
 }
 
 void BSSL_AMD_QUIC_SET_free(BSSL_AMD_QUIC_SET *s) {
   if (!s) return;
-  {
-    DeviceGuard g(s->km->device);
-    // As free_keys: drain the device, wipe, drain, free.
-    hipDeviceSynchronize();
-    hipMemset(s->slots, 0, s->km->num_keys * sizeof(QuicSetSlot));
-    hipDeviceSynchronize();
-    hipFree(s->slots);
-  }
-  free_keys(s->km);
+  keyset_free(s->km, s->slots, sizeof(QuicSetSlot));
   delete s;
 }
 
@@ -340,75 +241,30 @@ int BSSL_AMD_QUIC_SET_set_slots(BSSL_AMD_QUIC_SET *s, size_t first, size_t n, co
   if (!on_key_device(km)) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const size_t key_len = km->aead->key_len;
-  const bool gcm = km->aead->kind == kAeadAesGcm;
-  // The expanded keys and the slots staged in host memory, wiped on every path
-  // once the copies have read them.
-  std::vector<uint8_t> host_keys;
+  // The slots staged in host memory, wiped on every path once the copy has
+  // read them.
   std::vector<QuicSetSlot> host_slots(n);
-  struct Wipe {
-    std::vector<uint8_t> &k;
-    std::vector<QuicSetSlot> &c;
-    ~Wipe() {
-      secure_zero(k.data(), k.size());
-      secure_zero(c.data(), c.size() * sizeof(QuicSetSlot));
-    }
-  } wipe{host_keys, host_slots};
+  Wiped wipe{host_slots.data(), n * sizeof(QuicSetSlot)};
   bool ok = true;
   for (size_t i = 0; i < n && ok; i++) {
     QuicSetSlot &c = host_slots[i];
     memset(&c, 0, sizeof(c));
     c.pn = numbers ? numbers[i] : 0;
-    const uint8_t *iv = ivs + 12 * i;
-    for (int k = 0; k < 8; k++) c.iv_lo |= (uint64_t)iv[k] << (8 * k);
-    for (int k = 8; k < 12; k++) c.iv_hi |= (uint32_t)iv[k] << (8 * (k - 8));
+    pack_iv(ivs + 12 * i, 12, &c.iv_lo, &c.iv_hi);
     c.live = 1;
     // The header-protection key, expanded once as for one connection.
-    const uint8_t *hp = hp_keys + i * key_len;
-    if (s->mask == kDtlsMaskChaCha) {
-      for (int k = 0; k < 32; k++) c.hp[k / 4] |= (uint32_t)hp[k] << (8 * (k & 3));
-    } else {
-      CbcKeyDev ks;
-      ok = cbc_key_setup(hp, key_len, &ks);
-      memcpy(c.hp, ks.rk, sizeof(c.hp));
-      secure_zero(&ks, sizeof(ks));
-    }
+    ok = mask_key_words(s->mask, hp_keys + i * key_len, key_len, c.hp);
   }
-  if (ok && gcm && n >= kDeviceKeySetupMin) {
-    // The device key setup writes the tables straight into the slots (and
-    // waits for the stream).
-    ok = gcm_key_setup_device(keys, key_len, n, static_cast<GcmKeyDev *>(km->dev) + first, st) == 0;
-  } else if (ok) {
-    const size_t per = gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-    host_keys.resize(n * per);
-    for (size_t i = 0; i < n && ok; i++) {
-      if (gcm)
-        ok = gcm_key_setup(keys + i * key_len, key_len,
-                           reinterpret_cast<GcmKeyDev *>(host_keys.data()) + i);
-      else
-        chacha_key_setup(keys + i * key_len, reinterpret_cast<ChaChaKeyDev *>(host_keys.data()) + i);
-    }
-    ok = ok && hipMemcpyAsync(static_cast<uint8_t *>(km->dev) + first * per, host_keys.data(),
-                              n * per, hipMemcpyHostToDevice, st) == hipSuccess;
-  }
-  ok = ok && hipMemcpyAsync(s->slots + first, host_slots.data(), n * sizeof(QuicSetSlot),
-                            hipMemcpyHostToDevice, st) == hipSuccess;
-  // The copies read pageable host memory that is wiped on return: wait until
-  // they have.  (The host waits; the order on the stream is what the header
-  // promises either way.)
-  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
-  return finish(ok);
+  return finish(ok && install_slots(km, s->slots, sizeof(QuicSetSlot), first, n, keys,
+                                    host_slots.data(), st));
 }
 
 int BSSL_AMD_QUIC_SET_clear_slots(BSSL_AMD_QUIC_SET *s, size_t first, size_t n, void *hip_stream) {
   if (!range_ok(s, first, n)) return 0;
   if (n == 0) return 1;
-  KeyMaterial *km = s->km;
-  if (!on_key_device(km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t per = km->aead->kind == kAeadAesGcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-  return finish(
-      hipMemsetAsync(static_cast<uint8_t *>(km->dev) + first * per, 0, n * per, st) == hipSuccess &&
-      hipMemsetAsync(s->slots + first, 0, n * sizeof(QuicSetSlot), st) == hipSuccess);
+  if (!on_key_device(s->km)) return 0;
+  return finish(clear_slots(s->km, s->slots, sizeof(QuicSetSlot), first, n,
+                            reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
 int BSSL_AMD_QUIC_SET_next_packet_numbers(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
@@ -423,7 +279,7 @@ int BSSL_AMD_QUIC_SET_get_expected(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
 
 int BSSL_AMD_QUIC_SET_set_expected(BSSL_AMD_QUIC_SET *s, size_t first, size_t n,
                                    const uint64_t *expected, void *hip_stream) {
-  if (!range_ok(s, first, n) || !direction_ok(s, false)) return 0;
+  if (!range_ok(s, first, n) || !direction_ok(s->seal, false)) return 0;
   if (n == 0) return 1;
   if (!present(expected)) return 0;
   for (size_t i = 0; i < n; i++)

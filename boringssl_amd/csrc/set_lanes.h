@@ -1,7 +1,7 @@
 // set_lanes.h -- what the kernels over sets of peers (dtls_set.hip,
-// quic_set.hip) share beyond the claim scheme, which each states over its own
-// slot type: the workgroup's LDS of a kernel that computes masks with a key per
-// lane, and the prefix maximum of (run, number) pairs over a wave.
+// quic_set.hip) share beyond the run-to-slot frame (set_runs.h): the
+// workgroup's LDS of a kernel that computes masks with a key per lane, and the
+// prefix maximum of (run, number) pairs over a wave.
 #ifndef BSSL_AMD_SET_LANES_H
 #define BSSL_AMD_SET_LANES_H
 

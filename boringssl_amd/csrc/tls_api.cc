@@ -20,7 +20,7 @@
 
 #include "bssl_amd/tls.h"
 #include "bssl_amd/test_hooks.h"
-#include "api_internal.h"
+#include "set_api.h"
 
 using namespace bssl_amd;
 
@@ -55,12 +55,6 @@ struct TlsShape {
     *out = *this;
     out->padded = true;
     return true;
-  }
-  // A context or set of the other direction was called.
-  bool direction_ok(bool want_seal) const {
-    if (seal == want_seal) return true;
-    PUT_ERROR(CIPHER_R_INVALID_OPERATION);
-    return false;
   }
 };
 
@@ -104,42 +98,33 @@ const EVP_AEAD *tls_shape_init(TlsShape *sh, enum evp_aead_direction_t direction
   return rec_aead;
 }
 
-// The scratch of one call, one stream-ordered block: per record a padded
-// call's fragment length (8 bytes) and the set's key index (4 bytes; both
-// first: alignment), the nonce, the AD, the inner type (seal, TLS 1.3;
-// type_len 0: none), the flag, and a padded call's status byte for a caller
-// who passes none.  Freed in stream order on every path.
-struct TlsScratch {
-  hipStream_t s;
-  uint8_t *buf = nullptr;
-  uint64_t *frag_len = nullptr;
-  uint32_t *key_index = nullptr;
-  uint8_t *nonce = nullptr, *ad = nullptr, *type = nullptr, *valid = nullptr, *status = nullptr;
-  TlsScratch(hipStream_t stream, uint64_t n, uint32_t nonce_len, uint32_t ad_stride,
-             uint32_t type_len, bool keys, bool padded = false)
-      : s(stream) {
-    const uint32_t key_len = keys ? 4 : 0, frag = padded ? 8 : 0, status_len = padded ? 1 : 0;
-    if (bssl_amd::scratch_alloc(reinterpret_cast<void **>(&buf),
-                       n * (frag + key_len + nonce_len + ad_stride + type_len + 1 + status_len),
-                       s) != hipSuccess) {
-      buf = nullptr;
-      PUT_ERROR(ERR_R_MALLOC_FAILURE);
-      return;
-    }
-    if (padded) frag_len = reinterpret_cast<uint64_t *>(buf);
-    if (keys) key_index = reinterpret_cast<uint32_t *>(buf + frag * n);
-    nonce = buf + (frag + key_len) * n;
-    ad = nonce + nonce_len * n;
-    type = ad + ad_stride * n;
-    valid = type + type_len * n;
-    if (padded) status = valid + n;
+// The scratch of one call (one stream-ordered block, freed in stream order on
+// every path: CallScratch, set_api.h): per record a padded call's fragment
+// length and the set's key index (both first: alignment; null without), the
+// nonce, the AD, the inner type (seal, TLS 1.3; type_len 0: none), the flag,
+// and a padded call's status byte for a caller who passes none (else null).
+struct TlsLayout {
+  uint64_t n;
+  uint32_t nonce_len, ad_stride, type_len;
+  bool keys, padded;
+  uint64_t *frag_len;
+  uint32_t *key_index;
+  uint8_t *nonce, *ad, *type, *valid, *status;
+  TlsLayout(uint64_t records, uint32_t nonce_bytes, uint32_t ad_bytes, uint32_t type_bytes,
+            bool key_indices, bool is_padded = false)
+      : n(records), nonce_len(nonce_bytes), ad_stride(ad_bytes), type_len(type_bytes),
+        keys(key_indices), padded(is_padded) {}
+  void carve(Carver &c) {
+    frag_len = padded ? c.take<uint64_t>(n) : nullptr;
+    key_index = keys ? c.take<uint32_t>(n) : nullptr;
+    nonce = c.take<uint8_t>(nonce_len * n);
+    ad = c.take<uint8_t>(ad_stride * n);
+    type = c.take<uint8_t>(type_len * n);
+    valid = c.take<uint8_t>(n);
+    status = padded ? c.take<uint8_t>(n) : nullptr;
   }
-  ~TlsScratch() {
-    if (buf) bssl_amd::scratch_free(buf, s);
-  }
-  TlsScratch(const TlsScratch &) = delete;
-  TlsScratch &operator=(const TlsScratch &) = delete;
 };
+using TlsScratch = CallScratch<TlsLayout>;
 
 // The prepare step's inputs of an AEAD suite's batch, all but fixed_iv and seq
 // (one connection adds them; a set's come from its connections).
@@ -245,13 +230,6 @@ int tls_launch(bool ok, const KeyMaterial *km, const BatchDesc &d, const TlsShap
   }
   if (seq) *seq += d.num_records;
   return 1;
-}
-
-// A call without its context or set.
-bool present(const void *p) {
-  if (p) return true;
-  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-  return false;
 }
 
 // The null checks of a batch, and for a padded open the two outputs it exists
@@ -529,14 +507,14 @@ uint64_t BSSL_AMD_TLS_AEAD_sequence(const BSSL_AMD_TLS_AEAD *t) { return t->seq;
 
 int BSSL_AMD_TLS_AEAD_seal_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
                                           void *hip_stream) {
-  if (!present(t) || !t->shape.direction_ok(true)) return 0;
+  if (!present(t) || !direction_ok(t->shape.seal, true)) return 0;
   return t->cbc ? tls_cbc_records(t, r, hip_stream)
                 : tls_records(t, t->shape, r, nullptr, hip_stream);
 }
 
 int BSSL_AMD_TLS_AEAD_open_records_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
                                           void *hip_stream) {
-  if (!present(t) || !t->shape.direction_ok(false)) return 0;
+  if (!present(t) || !direction_ok(t->shape.seal, false)) return 0;
   return t->cbc ? tls_cbc_records(t, r, hip_stream)
                 : tls_records(t, t->shape, r, nullptr, hip_stream);
 }
@@ -545,14 +523,14 @@ int BSSL_AMD_TLS_AEAD_seal_tls13_padded_device(BSSL_AMD_TLS_AEAD *t, const BSSL_
                                                const BSSL_AMD_TLS13_PADDING *pad,
                                                void *hip_stream) {
   TlsShape sh;
-  if (!present(t) || !t->shape.padded_form(&sh) || !sh.direction_ok(true)) return 0;
+  if (!present(t) || !t->shape.padded_form(&sh) || !direction_ok(sh.seal, true)) return 0;
   return tls_records(t, sh, r, pad, hip_stream);
 }
 
 int BSSL_AMD_TLS_AEAD_open_tls13_padded_device(BSSL_AMD_TLS_AEAD *t, const BSSL_AMD_TLS_RECORDS *r,
                                                void *hip_stream) {
   TlsShape sh;
-  if (!present(t) || !t->shape.padded_form(&sh) || !sh.direction_ok(false)) return 0;
+  if (!present(t) || !t->shape.padded_form(&sh) || !direction_ok(sh.seal, false)) return 0;
   return tls_records(t, sh, r, nullptr, hip_stream);
 }
 
@@ -575,13 +553,6 @@ struct bssl_amd_tls_set_st {
 namespace {
 
 constexpr uint32_t kSetTagLen = 16;
-
-// Whether slots first .. first + n - 1 are inside the set.
-bool set_range_ok(const BSSL_AMD_TLS_SET *s, size_t first, size_t n) {
-  if (s && first <= s->km->num_keys && n <= s->km->num_keys - first) return true;
-  PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
-  return false;
-}
 
 // `sh`: the set's shape, or its padded form (then with `pad` on seal).
 int tls_set_records(BSSL_AMD_TLS_SET *t, const TlsShape &sh, const BSSL_AMD_TLS_SET_RECORDS *sr,
@@ -610,11 +581,9 @@ int tls_set_records(BSSL_AMD_TLS_SET *t, const TlsShape &sh, const BSSL_AMD_TLS_
   memset(&p, 0, sizeof(p));
   tls_fill_prepare(&p.rec, sh, r, sc, kSetTagLen);
   p.conns = t->conns;
-  p.num_connections = (uint32_t)km->num_keys;
-  p.num_runs = sr->num_runs;
-  p.run_connection = sr->run_connection;
-  p.run_start = sr->run_start;
-  p.key_index = sc.key_index;
+  // (No flag, run_of or run_won: the TLS frame is the lax one, set_runs.h.)
+  p.runs = {(uint32_t)km->num_keys, sr->num_runs, sr->run_connection, sr->run_start,
+            sc.key_index,           nullptr,      nullptr,            nullptr};
   ok = ok && launch_tls_set_prepare(p, stream) == 0;
   BatchDesc d = tls_batch_desc(r, sc, 12, sh.ad_stride(), kSetTagLen, sh);
   d.key_index = sc.key_index;
@@ -633,52 +602,22 @@ BSSL_AMD_TLS_SET *BSSL_AMD_TLS_SET_new(enum evp_aead_direction_t direction, uint
   if (!tls_shape_init(&sh, direction, version, aead,
                       num_connections != 0 && num_connections <= 0xfffffffeu))
     return nullptr;
-  const bool gcm = aead->kind == kAeadAesGcm;
-  int dev = 0;
   BSSL_AMD_TLS_SET *t = new (std::nothrow) bssl_amd_tls_set_st;
-  KeyMaterial *km =
-      t ? new (std::nothrow) KeyMaterial{aead, 0, num_connections, 0, nullptr, 0} : nullptr;
-  if (!km || hipGetDevice(&dev) != hipSuccess) {
-    delete km;
+  if (t)
+    t->km = keyset_new(aead, num_connections, sizeof(TlsSetConn),
+                       reinterpret_cast<void **>(&t->conns));
+  if (!t || !t->km) {
     delete t;
     PUT_ERROR(ERR_R_MALLOC_FAILURE);
     return nullptr;
   }
-  km->device = dev;
-  km->nr = gcm ? (int)aead->key_len / 4 + 6 : 0;
-  km->bytes = num_connections * (gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev));
-  t->km = km;
-  t->conns = nullptr;
   t->shape = sh;
-  // All slots unset: zero keys, zero state.
-  const size_t conn_bytes = num_connections * sizeof(TlsSetConn);
-  bool ok = hipMalloc(&km->dev, km->bytes) == hipSuccess;
-  if (!ok) km->dev = nullptr;
-  ok = ok && hipMalloc(reinterpret_cast<void **>(&t->conns), conn_bytes) == hipSuccess;
-  ok = ok && hipMemset(km->dev, 0, km->bytes) == hipSuccess &&
-       hipMemset(t->conns, 0, conn_bytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-  if (!ok) {
-    if (t->conns) hipFree(t->conns);
-    if (km->dev) hipFree(km->dev);
-    delete km;
-    delete t;
-    PUT_ERROR(ERR_R_MALLOC_FAILURE);
-    return nullptr;
-  }
   return t;
 }
 
 void BSSL_AMD_TLS_SET_free(BSSL_AMD_TLS_SET *s) {
   if (!s) return;
-  {
-    DeviceGuard g(s->km->device);
-    // As free_keys: drain the device, wipe, drain, free.
-    hipDeviceSynchronize();
-    hipMemset(s->conns, 0, s->km->num_keys * sizeof(TlsSetConn));
-    hipDeviceSynchronize();
-    hipFree(s->conns);
-  }
-  free_keys(s->km);
+  keyset_free(s->km, s->conns, sizeof(TlsSetConn));
   delete s;
 }
 
@@ -695,7 +634,7 @@ size_t BSSL_AMD_TLS_SET_suffix_len(const BSSL_AMD_TLS_SET *s) {
 int BSSL_AMD_TLS_SET_set_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
                                      const uint8_t *keys, const uint8_t *fixed_ivs,
                                      const uint64_t *seqs, void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
+  if (!range_ok(s, first, n)) return 0;
   if (n == 0) return 1;
   if (!keys || !fixed_ivs) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
@@ -703,127 +642,69 @@ int BSSL_AMD_TLS_SET_set_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n
   }
   KeyMaterial *km = s->km;
   if (!on_key_device(km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t key_len = km->aead->key_len;
   const size_t iv_len = s->shape.xor_nonce ? 12 : 4;
-  const bool gcm = km->aead->kind == kAeadAesGcm;
-  // The expanded keys and the connection state staged in host memory, wiped
-  // on every path once the copies have read them.
-  std::vector<uint8_t> host_keys;
+  // The connection state staged in host memory, wiped on every path once the
+  // copy has read it.
   std::vector<TlsSetConn> host_conns(n);
-  struct Wipe {
-    std::vector<uint8_t> &k;
-    std::vector<TlsSetConn> &c;
-    ~Wipe() {
-      secure_zero(k.data(), k.size());
-      secure_zero(c.data(), c.size() * sizeof(TlsSetConn));
-    }
-  } wipe{host_keys, host_conns};
+  Wiped wipe{host_conns.data(), n * sizeof(TlsSetConn)};
   for (size_t i = 0; i < n; i++) {
     TlsSetConn &c = host_conns[i];
     memset(&c, 0, sizeof(c));
     c.seq = seqs ? seqs[i] : 0;
-    uint8_t iv[12] = {0};
-    memcpy(iv, fixed_ivs + i * iv_len, iv_len);
-    for (int k = 0; k < 8; k++) c.iv_lo |= (uint64_t)iv[k] << (8 * k);
-    for (int k = 8; k < 12; k++) c.iv_hi |= (uint32_t)iv[k] << (8 * (k - 8));
-    secure_zero(iv, sizeof(iv));
+    pack_iv(fixed_ivs + i * iv_len, iv_len, &c.iv_lo, &c.iv_hi);
     c.live = 1;
   }
-  bool ok = true;
-  if (gcm && n >= kDeviceKeySetupMin) {
-    // The device key setup writes the tables straight into the slots (and
-    // waits for the stream).
-    ok = gcm_key_setup_device(keys, key_len, n, static_cast<GcmKeyDev *>(km->dev) + first, st) == 0;
-  } else {
-    const size_t per = gcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-    host_keys.resize(n * per);
-    for (size_t i = 0; i < n && ok; i++) {
-      if (gcm)
-        ok = gcm_key_setup(keys + i * key_len, key_len,
-                           reinterpret_cast<GcmKeyDev *>(host_keys.data()) + i);
-      else
-        chacha_key_setup(keys + i * key_len, reinterpret_cast<ChaChaKeyDev *>(host_keys.data()) + i);
-    }
-    ok = ok && hipMemcpyAsync(static_cast<uint8_t *>(km->dev) + first * per, host_keys.data(),
-                              n * per, hipMemcpyHostToDevice, st) == hipSuccess;
-  }
-  ok = ok && hipMemcpyAsync(s->conns + first, host_conns.data(), n * sizeof(TlsSetConn),
-                            hipMemcpyHostToDevice, st) == hipSuccess;
-  // The copies read pageable host memory that is wiped on return: wait until
-  // they have.  (The host waits; the order on the stream is what the header
-  // promises either way.)
-  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
+  return finish(install_slots(km, s->conns, sizeof(TlsSetConn), first, n, keys, host_conns.data(),
+                              reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
 int BSSL_AMD_TLS_SET_clear_connections(BSSL_AMD_TLS_SET *s, size_t first, size_t n,
                                        void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
+  if (!range_ok(s, first, n)) return 0;
   if (n == 0) return 1;
-  KeyMaterial *km = s->km;
-  if (!on_key_device(km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t per = km->aead->kind == kAeadAesGcm ? sizeof(GcmKeyDev) : sizeof(ChaChaKeyDev);
-  if (hipMemsetAsync(static_cast<uint8_t *>(km->dev) + first * per, 0, n * per, st) != hipSuccess ||
-      hipMemsetAsync(s->conns + first, 0, n * sizeof(TlsSetConn), st) != hipSuccess) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
+  if (!on_key_device(s->km)) return 0;
+  return finish(clear_slots(s->km, s->conns, sizeof(TlsSetConn), first, n,
+                            reinterpret_cast<hipStream_t>(hip_stream)));
 }
 
 int BSSL_AMD_TLS_SET_sequences(BSSL_AMD_TLS_SET *s, size_t first, size_t n, uint64_t *out,
                                void *hip_stream) {
-  if (!set_range_ok(s, first, n)) return 0;
+  if (!range_ok(s, first, n)) return 0;
   if (n == 0) return 1;
   if (!out) {
     PUT_ERROR(ERR_R_SHOULD_NOT_HAVE_BEEN_CALLED);
     return 0;
   }
   if (!on_key_device(s->km)) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  // The entries as they are (they hold the IVs too: wiped afterwards).
-  std::vector<TlsSetConn> host(n);
-  const bool ok = hipMemcpyAsync(host.data(), s->conns + first, n * sizeof(TlsSetConn),
-                                 hipMemcpyDeviceToHost, st) == hipSuccess &&
-                  hipStreamSynchronize(st) == hipSuccess;
-  for (size_t i = 0; i < n; i++) out[i] = ok ? host[i].seq : 0;
-  secure_zero(host.data(), n * sizeof(TlsSetConn));
-  if (!ok) {
-    PUT_ERROR(ERR_R_INTERNAL_ERROR);
-    return 0;
-  }
-  return 1;
+  const bool ok = copy_columns(s->conns, sizeof(TlsSetConn), first, n, offsetof(TlsSetConn, seq), 8,
+                               out, true, reinterpret_cast<hipStream_t>(hip_stream));
+  if (!ok) memset(out, 0, n * sizeof(uint64_t));
+  return finish(ok);
 }
 
 int BSSL_AMD_TLS_SET_seal_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                          void *hip_stream) {
-  if (!present(s) || !s->shape.direction_ok(true)) return 0;
+  if (!present(s) || !direction_ok(s->shape.seal, true)) return 0;
   return tls_set_records(s, s->shape, r, nullptr, hip_stream);
 }
 
 int BSSL_AMD_TLS_SET_open_records_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                          void *hip_stream) {
-  if (!present(s) || !s->shape.direction_ok(false)) return 0;
+  if (!present(s) || !direction_ok(s->shape.seal, false)) return 0;
   return tls_set_records(s, s->shape, r, nullptr, hip_stream);
 }
 
 int BSSL_AMD_TLS_SET_seal_tls13_padded_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                               const BSSL_AMD_TLS13_PADDING *pad, void *hip_stream) {
   TlsShape sh;
-  if (!present(s) || !s->shape.padded_form(&sh) || !sh.direction_ok(true)) return 0;
+  if (!present(s) || !s->shape.padded_form(&sh) || !direction_ok(sh.seal, true)) return 0;
   return tls_set_records(s, sh, r, pad, hip_stream);
 }
 
 int BSSL_AMD_TLS_SET_open_tls13_padded_device(BSSL_AMD_TLS_SET *s, const BSSL_AMD_TLS_SET_RECORDS *r,
                                               void *hip_stream) {
   TlsShape sh;
-  if (!present(s) || !s->shape.padded_form(&sh) || !sh.direction_ok(false)) return 0;
+  if (!present(s) || !s->shape.padded_form(&sh) || !direction_ok(sh.seal, false)) return 0;
   return tls_set_records(s, sh, r, nullptr, hip_stream);
 }
 

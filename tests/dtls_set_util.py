@@ -49,7 +49,7 @@ class SetModel:
 
 
 def find_run(run_start, i):
-    """dtls_set_prepare_kernel's search, literally: the last run that starts at
+    """set_lane()'s search (set_runs.h), literally: the last run that starts at
     or before record i; always below len(run_start) - 1."""
     lo, hi = 0, len(run_start) - 1
     while hi - lo > 1:
@@ -62,7 +62,7 @@ def find_run(run_start, i):
 
 
 def malformed(run_start, n):
-    """dtls_set_claim_kernel's check, run by run."""
+    """set_claim_kernel's check (set_runs.h), run by run."""
     num_runs = len(run_start) - 1
     return any(run_start[j + 1] < run_start[j] or (j == 0 and run_start[0] != 0) or
                (j + 1 == num_runs and run_start[j + 1] != n) for j in range(num_runs))
